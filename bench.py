@@ -9,6 +9,11 @@ deploy -> inject TASK_FAILED (restart MTTR) -> ``pod replace`` (replace MTTR) ->
 ``value`` is the mean deploy-plan COMPLETE wall-clock over the K timed steps (seconds, lower is
 better); the MTTRs are reported alongside. Weak scaling: one pod per GPU.
 
+A plain run sets up, warms up, times the K steps and prints one JSON line. ``--full`` adds what the
+headline figure does not need (the ``reference_spec`` row: the reference's serial ``gpu_resource.yml``
+scenario on the same agents, after the timed region). ``--dump-outputs DIR`` writes what the last
+timed step computed as ``DIR/<name>.npy``.
+
 Under ``torchrun`` every rank owns the agent for its GPU (LOCAL_RANK) and rank 0 runs the
 master + scheduler; agents talk to the master over TCP (``parallel.agent_link``).
 """
@@ -42,9 +47,17 @@ def parse_args(argv=None):
                     help="scheduler flag override on top of --profile (A/B experiments)")
     ap.add_argument("--no-pin", action="store_true",
                     help="do not pin each rank to its own slice of the allowed CPUs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run what the headline figure does not need: the "
+                         "`reference_spec` row (see --reference-steps). A plain run sets up, warms up, times "
+                         "--steps steps and prints the result line")
     ap.add_argument("--reference-steps", type=int, default=None,
-                    help="cycles of the reference's unchanged gpu_resource.yml (default serial deploy) run after "
-                         "the timed region and reported as `reference_spec` (default: --steps; 0 = skip)")
+                    help="with --full: cycles of the reference's unchanged gpu_resource.yml (default serial "
+                         "deploy) run after the timed region and reported as `reference_spec` (default: --steps; "
+                         "0 = skip)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (placement, task states, "
+                         "deploy plan step statuses) as DIR/<name>.npy")
     ap.add_argument("--topology", default="split", choices=["split", "inprocess"],
                     help="split: the master and every agent's task lifecycle run in processes of their own (a "
                          "master process; each rank, or a helper process per agent, runs its tasks), the "

@@ -25,6 +25,7 @@ from dcos_commons_amd.framework.process_exit import ProcessExit
 from dcos_commons_amd.mesos import protos as P
 from dcos_commons_amd.mesos.local_master import AgentSpec, LocalMaster, LocalSchedulerDriver, TaskBehavior, TaskTiming
 from dcos_commons_amd.offer.taskdata.labels import TaskLabelReader
+from dcos_commons_amd.scheduler.plan.status import Status
 from dcos_commons_amd.scheduler.scheduler_builder import SchedulerBuilder
 from dcos_commons_amd.scheduler.scheduler_config import SchedulerConfig
 from dcos_commons_amd.scheduler.scheduler_runner import SchedulerRunner
@@ -166,6 +167,8 @@ class DeployBench:
         if master_client is None and len(self.agent_specs) != n_agents:
             raise ValueError(f"{len(self.agent_specs)} agent specs for {n_agents} agents")
         self.last_placement: List[Dict] = []  # LocalMaster.placement() once the last deploy completed
+        self.capture_outputs = False          # keep what each cycle computed (_cycle_outputs) ...
+        self.last_outputs: Optional[Dict[str, List[List[float]]]] = None     # ... of the last one, here
         self.allocation_interval_s = allocation_interval_s
         self.timeout_s = timeout_s
         self.agent_runners = agent_runners  # per-agent check runner (remote GPU agents)
@@ -217,6 +220,39 @@ class DeployBench:
         r = router.get(f"/v1/plans/{plan}")
         if r.status != 200:
             raise RuntimeError(f"/v1/plans/{plan} answered {r.status} after the plan completed")
+
+    def _cycle_outputs(self, sched, state_store) -> Dict[str, List[List[float]]]:
+        """What a finished cycle computed, as rows of numbers that do not depend on timing
+        (``bench.py --dump-outputs``):
+
+        * ``placement``: one row per GPU a live task held once the deploy completed, ``[agent,
+          device]`` (agent: index of its hostname among the sorted hostnames), rows sorted, so the
+          rows do not depend on which pod an agent's offer happened to serve;
+        * ``task_states``: one row per task in name order at the end of the cycle (after the restart
+          and the replace), ``[TaskState, readiness check succeeded]``;
+        * ``plans``: ``[plan, phase, step, status]`` for the deploy plan (0), each of its phases
+          (step -1) and steps, and the recovery plan (1) as a whole (phase -1, step -1); status is
+          the index into ``Status``."""
+        hosts = sorted({x["hostname"] for x in self.last_placement})
+        placement = sorted([float(hosts.index(x["hostname"])), float(dev)]
+                           for x in self.last_placement for dev in x["gpu_devices"])
+        states = []
+        for name in sorted(state_store.fetch_task_names()):
+            info, st = state_store.fetch_task_shared(name), state_store.fetch_status(name)
+            ready = info is not None and st is not None and TaskLabelReader(info).is_readiness_check_succeeded(st)
+            states.append([float(st.state) if st is not None else -1.0, float(ready)])
+        codes = list(Status)
+        plans = []
+        for p, name in enumerate(("deploy", "recovery")):
+            plan = sched.get_plan(name)
+            plans.append([float(p), -1.0, -1.0, float(codes.index(plan.get_status()))])
+            if name != "deploy":
+                continue    # finished recovery phases are the recovery manager's to drop or keep
+            for i, phase in enumerate(plan.get_children()):
+                plans.append([float(p), float(i), -1.0, float(codes.index(phase.get_status()))])
+                plans.extend([float(p), float(i), float(j), float(codes.index(step.get_status()))]
+                             for j, step in enumerate(phase.get_children()))
+        return {"placement": placement, "task_states": states, "plans": plans}
 
     def _make_master(self) -> "_Cluster":
         if self.master_client is not None:
@@ -294,6 +330,8 @@ class DeployBench:
                        self._plan_done(sched, "recovery"), "replace recovery", ev)
             mttr_replace = time.perf_counter() - t2
             self._expect_api(router, "recovery")
+            if self.capture_outputs:
+                self.last_outputs = self._cycle_outputs(sched, state_store)
         finally:
             runner.stop()
             master.shutdown()

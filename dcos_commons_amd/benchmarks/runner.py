@@ -96,11 +96,12 @@ def _reference_row(args, n, make_bench) -> dict:
     """BASELINE config #5 as the reference itself would run it: its unchanged helloworld
     ``gpu_resource.yml`` (``gpus: 1`` hello pods, ``hostname:UNIQUE``, no ``plans:`` so the default
     *serial* deploy of DeployPlanFactory.java:22 / DefaultPhaseFactory.java:35, no readiness
-    check), on the same agents, after the timed region (it does not enter ``value``/``ms_per_step``)."""
+    check), on the same agents, after the timed region (it does not enter ``value``/``ms_per_step``).
+    Only under ``--full``: the headline figure does not need it."""
     steps = getattr(args, "reference_steps", 0)
-    path = reference_spec("gpu_resource.yml")
-    if steps <= 0:
+    if not getattr(args, "full", False) or steps <= 0:
         return {}
+    path = reference_spec("gpu_resource.yml")
     if path is None:
         # the repository's rewrite of the same scenario (also no plans: -> serial)
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))),
@@ -124,6 +125,23 @@ def _reference_row(args, n, make_bench) -> dict:
 
 # the reference example's world pods are not part of BASELINE config #5 (hello pods, one per GPU)
 REFERENCE_ROW_ENV = {"WORLD_COUNT": "0"}
+
+
+def _dump_outputs(args, bench) -> None:
+    """``--dump-outputs DIR``: what the last timed cycle computed (``DeployBench._cycle_outputs``:
+    placement, task states, plan statuses; a few rows each) as ``DIR/<name>.npy``, float64. The
+    bench's inputs (spec, environment, agents) are fixed by its arguments and nothing in these rows
+    is a time, so two builds run with the same arguments can be compared file by file."""
+    path = getattr(args, "dump_outputs", None)
+    if not path:
+        return
+    import numpy as np
+
+    if bench.last_outputs is None:
+        raise SystemExit("--dump-outputs: no timed step ran")
+    os.makedirs(path, exist_ok=True)
+    for name, rows in bench.last_outputs.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.asarray(rows, dtype=np.float64))
 
 
 def _record(path, payload) -> None:
@@ -151,6 +169,7 @@ def _run_single(args, n, use_gpu):
                            allocation_interval_s=args.allocation_interval, extra_env=_sched_env(args),
                            agent_specs=specs, spec_file=spec_file, spec_env=spec_env)
     bench = make()
+    bench.capture_outputs = bool(getattr(args, "dump_outputs", None))
     for _ in range(args.warmup):
         bench.run_cycle()
     _sync()
@@ -158,6 +177,7 @@ def _run_single(args, n, use_gpu):
     cycles = [bench.run_cycle() for _ in range(args.steps)]
     _sync()
     elapsed = time.perf_counter() - t0
+    _dump_outputs(args, bench)
     out = _summary(args, n, cycles, elapsed, use_gpu, f"agents{n}")
     out["config"]["agent_attributes"] = specs[0].attributes
     out.update(_reference_row(args, n, lambda path: make(path, REFERENCE_ROW_ENV)))
@@ -254,6 +274,7 @@ def _run_distributed(args, rank, world, local_rank, use_gpu, dist):
                            allocation_interval_s=args.allocation_interval, extra_env=_sched_env(args),
                            spec_file=spec_file, spec_env=spec_env)
     bench = make()
+    bench.capture_outputs = bool(getattr(args, "dump_outputs", None))
     for _ in range(args.warmup):
         bench.run_cycle()
 
@@ -268,6 +289,7 @@ def _run_distributed(args, rank, world, local_rank, use_gpu, dist):
     _sync()
     barrier()
     elapsed = time.perf_counter() - t0
+    _dump_outputs(args, bench)
     placement = bench.last_placement
     extra = _reference_row(args, world, lambda path: make(path, REFERENCE_ROW_ENV))
     server.close()
@@ -341,6 +363,7 @@ def _run_single_split(args, n, use_gpu, cluster):
         return DeployBench(n, profile=args.profile, allocation_interval_s=args.allocation_interval,
                            extra_env=_sched_env(args), spec_file=spec_file, spec_env=spec_env, master_client=client)
     bench = make()
+    bench.capture_outputs = bool(getattr(args, "dump_outputs", None))
     for _ in range(args.warmup):
         bench.run_cycle()
     _sync()
@@ -348,6 +371,7 @@ def _run_single_split(args, n, use_gpu, cluster):
     cycles = [bench.run_cycle() for _ in range(args.steps)]
     _sync()
     elapsed = time.perf_counter() - t0
+    _dump_outputs(args, bench)
     out = _split_summary(args, n, cycles, elapsed, use_gpu, f"agents{n}", infos)
     out["config"]["agent_processes"] = n
     out["config"]["devices"] = [i % max(1, ndev) for i in range(n)]
@@ -411,6 +435,7 @@ def _run_distributed_split(args, rank, world, local_rank, use_gpu, dist, cluster
         return DeployBench(world, profile=args.profile, allocation_interval_s=args.allocation_interval,
                            extra_env=_sched_env(args), spec_file=spec_file, spec_env=spec_env, master_client=client)
     bench = make()
+    bench.capture_outputs = bool(getattr(args, "dump_outputs", None))
     for _ in range(args.warmup):
         bench.run_cycle()
     barrier()
@@ -418,6 +443,7 @@ def _run_distributed_split(args, rank, world, local_rank, use_gpu, dist, cluster
     cycles = [bench.run_cycle() for _ in range(args.steps)]
     barrier()
     elapsed = time.perf_counter() - t0
+    _dump_outputs(args, bench)
     placement = bench.last_placement
     extra = _reference_row(args, world, lambda path: make(path, REFERENCE_ROW_ENV))
     t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)

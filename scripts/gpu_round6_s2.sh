@@ -8,10 +8,10 @@ mkdir -p $out/prof
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > $out/pytest_gpu.txt 2>&1 && \
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.txt 2>&1 || exit $?
 for r in 1 2; do
-  timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 > $out/bench_n1_r$r.json 2> $out/bench_n1_r$r.err || exit $?
+  timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 --full > $out/bench_n1_r$r.json 2> $out/bench_n1_r$r.err || exit $?
   for n in 2 4 8; do
     timeout -k 10 240 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
-      --master-port $((29600 + n + RANDOM % 200)) bench.py --gpus $n --steps 20 --warmup 3 --dist-backend gloo \
+      --master-port $((29600 + n + RANDOM % 200)) bench.py --gpus $n --steps 20 --warmup 3 --dist-backend gloo --full \
       > $out/scale_n${n}_r$r.json 2> $out/scale_n${n}_r$r.err || exit $?
   done
 done

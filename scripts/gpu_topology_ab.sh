@@ -9,12 +9,12 @@ mkdir -p $out
 run() {  # topology n round
   local t=$1 n=$2 r=$3
   if [ "$n" = 1 ]; then
-    timeout -k 10 200 python -u bench.py --steps ${STEPS:-10} --warmup 2 --topology $t --reference-steps 2 \
+    timeout -k 10 200 python -u bench.py --steps ${STEPS:-10} --warmup 2 --topology $t --full --reference-steps 2 \
       > $out/${t}_n${n}_r${r}.json 2> $out/${t}_n${n}_r${r}.err
   else
     timeout -k 10 240 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
       --master-port $((29600 + n + 10 * r)) bench.py --gpus $n --steps ${STEPS:-10} --warmup 2 --dist-backend gloo \
-      --topology $t --reference-steps 2 > $out/${t}_n${n}_r${r}.json 2> $out/${t}_n${n}_r${r}.err
+      --topology $t --full --reference-steps 2 >$out/${t}_n${n}_r${r}.json 2> $out/${t}_n${n}_r${r}.err
   fi
 }
 for r in 1 2; do

@@ -50,6 +50,36 @@ def test_bench_single_process():
     recs = _json_lines(p.stdout)
     assert len(recs) == 1
     _check(recs[0], 1, 1, 0)
+    assert "reference_spec" not in recs[0]      # a plain run stops after its timed steps (--full adds the row)
+
+
+def test_bench_dump_outputs_repeat_run_for_run(tmp_path):
+    """``--dump-outputs``: two runs with the same arguments write the same float64 arrays (what
+    the last timed cycle computed: placement, task states, plan statuses), and the result line still
+    reports the steps asked for."""
+    import numpy as np
+
+    from dcos_commons_amd.mesos import protos as P
+    from dcos_commons_amd.scheduler.plan.status import Status
+
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    dumps = []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "0",
+                            "--no-gpu-probe", "--allocation-interval", "0.05", "--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        _check(_json_lines(p.stdout)[0], 2, 2, 0)
+        dumps.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = dumps
+    assert sorted(a) == sorted(b) == ["placement.npy", "plans.npy", "task_states.npy"]
+    for f in a:
+        assert a[f].dtype == np.float64 and a[f].shape == b[f].shape and (a[f] == b[f]).all(), f
+    # one GPU per pod, one pod per agent; both pods RUNNING and ready after the restart and the replace
+    assert a["placement.npy"][:, 0].tolist() == [0.0, 1.0]
+    assert a["task_states.npy"].tolist() == [[float(P.TASK_RUNNING), 1.0]] * 2
+    complete = float(list(Status).index(Status.COMPLETE))
+    assert a["plans.npy"].shape[1] == 4 and (a["plans.npy"][:, 3] == complete).all()
 
 
 @pytest.mark.timeout(400)
@@ -70,7 +100,7 @@ def test_bench_four_ranks_build_agents_from_what_each_rank_registers(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--no-gpu-probe",
-           "--allocation-interval", "0.05", "--reference-steps", "1"]
+           "--allocation-interval", "0.05", "--full", "--reference-steps", "1"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=380, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     recs = _json_lines(p.stdout)
@@ -155,7 +185,7 @@ def test_bench_single_process_with_agent_processes(tmp_path):
     record = tmp_path / "record"
     env = dict(os.environ, PYTHONPATH=ROOT, SDK_BENCH_RECORD=str(record))
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "1", "--warmup", "1",
-                        "--no-gpu-probe", "--allocation-interval", "0.05", "--reference-steps", "1",
+                        "--no-gpu-probe", "--allocation-interval", "0.05", "--full", "--reference-steps", "1",
                         "--agent0", "thread"],
                        capture_output=True, text=True, timeout=280, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
