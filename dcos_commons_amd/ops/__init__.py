@@ -1,7 +1,8 @@
 """MI355X device ops: HIP probe kernels behind a torch-tensor API.
 
 The kernels live in ``csrc/probe_kernels.hip`` (MFMA bf16 GEMM, MFMA issue-rate loop, HBM
-streaming copy, HBM pattern test) and are compiled for gfx950 into the in-tree
+streaming copy, HBM pattern test) and ``csrc/f8_kernels.hip`` (FP8 / MXFP8 MFMA GEMM and its
+dense VALU check) and are compiled for gfx950 into the in-tree
 ``_amdprobe.so`` (``python -m dcos_commons_amd.ops.build``). They back the GPU readiness/health
 check that gates pods which request ``gpus`` (``dcos_commons_amd.ops.gpu_health``).
 
@@ -56,6 +57,14 @@ def _bind(lib: ctypes.CDLL) -> None:
     lib.amdprobe_readiness_fill.restype = i
     lib.amdprobe_readiness.argtypes = [i, ctypes.c_uint, i, ctypes.POINTER(d), ctypes.POINTER(ctypes.c_ulonglong)]
     lib.amdprobe_readiness.restype = i
+    lib.amdprobe_gemm_f8_nt.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp, vp]
+    lib.amdprobe_gemm_f8_nt.restype = i
+    lib.amdprobe_gemm_f8_check.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp, i, vp, vp]
+    lib.amdprobe_gemm_f8_check.restype = i
+    lib.amdprobe_f8_fill.argtypes = [vp, sz, ctypes.c_uint, i, vp, vp]
+    lib.amdprobe_f8_fill.restype = i
+    lib.amdprobe_readiness_f8.argtypes = [i, ctypes.c_uint, i, i, ctypes.POINTER(d)]
+    lib.amdprobe_readiness_f8.restype = i
 
 
 def lib() -> ctypes.CDLL:
@@ -195,6 +204,101 @@ def readiness(device: int = 0, seed: int = 0, inject: int = 0):
     _check(lib().amdprobe_readiness(int(device), seed & 0xFFFFFFFF, int(inject), ctypes.byref(rel),
                                     ctypes.byref(bad)), "readiness")
     return rel.value, int(bad.value)
+
+
+F8_TILE = 128                       # M, N and K granule of gemm_f8_nt
+F8_BLOCK = 32                       # K elements per E8M0 block scale
+F8_FILL_KINDS = {"e4m3": 0, "e5m2": 1, "scale": 2}
+READINESS_F8_MODES = {"fp8": 0, "bf8": 1, "mxfp8": 2}
+
+
+def _f8_operands(what: str, a, bt, a_scale, bt_scale, granule: int, k_granule: int):
+    """Validates fp8 operands (and block scales) before native code sees them; returns
+    ``(a, bt, fmt_a, fmt_b, a_scale, bt_scale, m, n, k)`` with contiguous tensors."""
+    import torch
+
+    fmts = {torch.float8_e4m3fn: 0, torch.float8_e5m2: 1}
+    if a.dtype not in fmts or bt.dtype not in fmts:
+        raise ProbeError(f"{what} expects float8_e4m3fn / float8_e5m2 operands, got {a.dtype} and {bt.dtype}")
+    fa, fb = fmts[a.dtype], fmts[bt.dtype]
+    if (fa, fb) == (1, 0):
+        raise ProbeError(f"{what}: E5M2 x E4M3 is not built (swap the operands: E4M3 x E5M2 is)")
+    if a.dim() != 2 or bt.dim() != 2 or a.shape[1] != bt.shape[1]:
+        raise ProbeError(f"{what} shape mismatch: {tuple(a.shape)} x {tuple(bt.shape)}^T")
+    m, k = a.shape
+    n = bt.shape[0]
+    if m % granule or n % granule or k % k_granule:
+        raise ProbeError(f"{what} needs M,N % {granule} == 0 and K % {k_granule} == 0, got {m}x{n}x{k}")
+    if (a_scale is None) != (bt_scale is None):
+        raise ProbeError(f"{what}: block scales come in pairs (a_scale and bt_scale, or neither)")
+    if a_scale is not None:
+        for name, sc, rows in (("a_scale", a_scale, m), ("bt_scale", bt_scale, n)):
+            if sc.dtype != torch.uint8 or tuple(sc.shape) != (rows, k // F8_BLOCK):
+                raise ProbeError(f"{what}: {name} must be uint8 [{rows}, {k // F8_BLOCK}], got {sc.dtype} "
+                                 f"{tuple(sc.shape)}")
+        a_scale, bt_scale = a_scale.contiguous(), bt_scale.contiguous()
+    return a.contiguous(), bt.contiguous(), fa, fb, a_scale, bt_scale, m, n, k
+
+
+def gemm_f8_nt(a, bt, a_scale=None, bt_scale=None, out=None):
+    """``a[M,K] @ bt[N,K]^T`` in fp32 on the FP8 MFMA kernel (``v_mfma_f32_16x16x128_f8f6f4``);
+    M, N, K % 128 == 0. ``a`` / ``bt`` are ``float8_e4m3fn`` or ``float8_e5m2`` (E4M3 x E4M3,
+    E5M2 x E5M2, E4M3 x E5M2). With ``a_scale[M, K/32]`` and ``bt_scale[N, K/32]`` (uint8 E8M0, value
+    ``2^(s - 127)`` per 32 K elements) the product is MX block-scaled by the instruction's scale
+    inputs (``v_mfma_scale_f32_16x16x128_f8f6f4``)."""
+    import torch
+
+    a, bt, fa, fb, a_scale, bt_scale, m, n, k = _f8_operands("gemm_f8_nt", a, bt, a_scale, bt_scale, F8_TILE,
+                                                              F8_TILE)
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.float32, device=a.device)
+    sa = a_scale.data_ptr() if a_scale is not None else None
+    sb = bt_scale.data_ptr() if bt_scale is not None else None
+    _check(lib().amdprobe_gemm_f8_nt(a.data_ptr(), bt.data_ptr(), out.data_ptr(), m, n, k, fa, fb, sa, sb,
+                                     _stream(a.device)), "gemm_f8_nt")
+    return out
+
+
+def gemm_f8_check(a, bt, c, a_scale=None, bt_scale=None, inject: int = 0):
+    """Dense check of an FP8 (or MX block-scaled) product ``c`` on the GPU, every element against an
+    fp32 VALU reference that never touches the matrix pipe: returns ``(sum((c - ref)^2), sum(ref^2))``.
+    M, N % 16 == 0, K % 32 == 0, K <= 1024."""
+    import torch
+
+    a, bt, fa, fb, a_scale, bt_scale, m, n, k = _f8_operands("gemm_f8_check", a, bt, a_scale, bt_scale, 16,
+                                                              F8_BLOCK)
+    if c.dtype != torch.float32 or tuple(c.shape) != (m, n):
+        raise ProbeError(f"gemm_f8_check: c must be float32 {(m, n)}, got {c.dtype} {tuple(c.shape)}")
+    c = c.contiguous()
+    out = torch.zeros(4, dtype=torch.float32, device=a.device)
+    sa = a_scale.data_ptr() if a_scale is not None else None
+    sb = bt_scale.data_ptr() if bt_scale is not None else None
+    _check(lib().amdprobe_gemm_f8_check(a.data_ptr(), bt.data_ptr(), c.data_ptr(), m, n, k, fa, fb, sa, sb, inject,
+                                        out.data_ptr(), _stream(a.device)), "gemm_f8_check")
+    o = out.cpu()
+    return float(o[0]), float(o[1])
+
+
+def f8_fill(buf, seed: int, kind: str = "e4m3"):
+    """The FP8 readiness operand fill into ``buf`` (byte size % 16): finite hashed ``e4m3`` / ``e5m2``
+    bytes with |x| in [0.5, 1), or E8M0 block ``scale`` bytes in [124, 131]."""
+    if kind not in F8_FILL_KINDS:
+        raise ProbeError(f"unknown f8 fill {kind!r}: {sorted(F8_FILL_KINDS)}")
+    _check(lib().amdprobe_f8_fill(buf.data_ptr(), buf.numel() * buf.element_size(), seed & 0xFFFFFFFF,
+                                  F8_FILL_KINDS[kind], None, _stream(buf.device)), "f8_fill")
+
+
+def readiness_f8(device: int = 0, seed: int = 0, mode: str = "fp8", inject: int = 0) -> float:
+    """The FP8 matrix path of one device in one native call: hashed operands, the f8 MFMA GEMM (``fp8`` =
+    E4M3, ``bf8`` = E5M2, ``mxfp8`` = E4M3 with E8M0 block scales through the MFMA scale inputs), the dense
+    VALU check of every element, one read-back on a private stream. Returns ``gemm_rel_err``. ``inject`` = 1
+    loses a product tile, 3 skips the GEMM (tests). The GIL is released for the duration (ctypes)."""
+    if mode not in READINESS_F8_MODES:
+        raise ProbeError(f"unknown f8 readiness mode {mode!r}: {sorted(READINESS_F8_MODES)}")
+    rel = ctypes.c_double(0.0)
+    _check(lib().amdprobe_readiness_f8(int(device), seed & 0xFFFFFFFF, READINESS_F8_MODES[mode], int(inject),
+                                       ctypes.byref(rel)), "readiness_f8")
+    return rel.value
 
 
 def require_native_on_gpu() -> None:

@@ -26,6 +26,9 @@ NATIVE = os.path.join(ROOT, "native")
 BUILD = os.path.join(NATIVE, "build")
 BUILD_SANITIZE = os.path.join(NATIVE, "build-sanitize")  # ASan/UBSan host tools (tests only)
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0] or "gfx950"
+KERNEL_SRCS = ("probe_kernels.hip", "f8_kernels.hip")  # #included by probe_api.hip
+# no packed-fp32 VALU forms (v_pk_fma_f32 and kin) in the kernels' scalar fp32 math
+DEVICE_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 
 def hipcc() -> str:
@@ -52,9 +55,10 @@ def _run(cmd: List[str], verbose: bool) -> None:
 
 def build_probe_lib(force: bool = False, verbose: bool = False) -> str:
     out = os.path.join(OPS, "_amdprobe.so")
-    srcs = [os.path.join(OPS, "csrc", f) for f in ("probe_api.hip", "probe_kernels.hip")]
+    srcs = [os.path.join(OPS, "csrc", f) for f in ("probe_api.hip",) + KERNEL_SRCS]
     if force or _stale(out, srcs):
-        _run([hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", srcs[0], "-o", out], verbose)
+        _run([hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", *DEVICE_FLAGS, "-fPIC", "-shared", srcs[0],
+              "-o", out], verbose)
     return out
 
 
@@ -73,9 +77,10 @@ def build_probe_service(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(BUILD, exist_ok=True)
     out = os.path.join(BUILD, "amd-gpu-probed")
     srcs = [os.path.join(NATIVE, "probe", "probed.cpp"), os.path.join(OPS, "csrc", "probe_api.hip")]
-    deps = srcs + [os.path.join(OPS, "csrc", "probe_kernels.hip")]
+    deps = srcs + [os.path.join(OPS, "csrc", f) for f in KERNEL_SRCS]
     if force or _stale(out, deps):
-        _run([hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-pthread", *srcs, "-o", out], verbose)
+        _run([hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", *DEVICE_FLAGS, "-pthread", *srcs, "-o", out],
+             verbose)
     return out
 
 

@@ -3,6 +3,7 @@
 // the kernel's grid assumes before launching and returns a hipError_t (0 = success) or a
 // negative code for a rejected shape.
 #include "probe_kernels.hip"
+#include "f8_kernels.hip"
 
 #include <cmath>
 #include <mutex>
@@ -232,5 +233,166 @@ AMDPROBE_EXPORT int amdprobe_readiness(int device, unsigned seed, int inject, do
   const double d2 = ctx.host->diff2, w2 = ctx.host->ref2;
   *rel_err = (w2 > 0.0 && std::isfinite(d2)) ? std::sqrt(d2 / w2) : HUGE_VAL;  // NaN C (never written) fails
   *bad_words = ctx.host->bad_words;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// FP8 / MXFP8 (f8_kernels.hip). fmt_a / fmt_b: 0 = E4M3, 1 = E5M2 (OCP); the pairs built are
+// E4M3 x E4M3, E5M2 x E5M2 and E4M3 x E5M2. sa / sb: E8M0 block scales [M][K/32], [N][K/32], both
+// null for an unscaled product.
+// ---------------------------------------------------------------------------------------
+namespace {
+template <bool MX>
+int launch_gemm_f8(const uint8_t* A, const uint8_t* Bt, float* C, const uint8_t* sa, const uint8_t* sb, int M, int N,
+                   int K, int fmt_a, int fmt_b, hipStream_t s) {
+  const dim3 grid((M / f8::BM) * (N / f8::BN)), block(f8::THREADS);
+  if (fmt_a == F8_E4M3 && fmt_b == F8_E4M3)
+    hipLaunchKernelGGL((gemm_f8_nt_kernel<F8_E4M3, F8_E4M3, MX>), grid, block, 0, s, A, Bt, C, sa, sb, M, N, K);
+  else if (fmt_a == F8_E5M2 && fmt_b == F8_E5M2)
+    hipLaunchKernelGGL((gemm_f8_nt_kernel<F8_E5M2, F8_E5M2, MX>), grid, block, 0, s, A, Bt, C, sa, sb, M, N, K);
+  else if (fmt_a == F8_E4M3 && fmt_b == F8_E5M2)
+    hipLaunchKernelGGL((gemm_f8_nt_kernel<F8_E4M3, F8_E5M2, MX>), grid, block, 0, s, A, Bt, C, sa, sb, M, N, K);
+  else
+    return ERR_SHAPE;
+  return (int)hipGetLastError();
+}
+}  // namespace
+
+AMDPROBE_EXPORT int amdprobe_gemm_f8_nt(const void* A, const void* Bt, float* C, int M, int N, int K, int fmt_a,
+                                        int fmt_b, const void* sa, const void* sb, void* stream) {
+  if (M <= 0 || N <= 0 || K <= 0 || M % f8::BM || N % f8::BN || K % f8::BK) return ERR_SHAPE;
+  if ((sa == nullptr) != (sb == nullptr)) return ERR_SHAPE;
+  if (!aligned16(A) || !aligned16(Bt) || !aligned16(C) || !aligned16(sa) || !aligned16(sb)) return ERR_ALIGN;
+  const uint8_t *a = (const uint8_t*)A, *b = (const uint8_t*)Bt, *pa = (const uint8_t*)sa, *pb = (const uint8_t*)sb;
+  return sa != nullptr ? launch_gemm_f8<true>(a, b, C, pa, pb, M, N, K, fmt_a, fmt_b, (hipStream_t)stream)
+                       : launch_gemm_f8<false>(a, b, C, pa, pb, M, N, K, fmt_a, fmt_b, (hipStream_t)stream);
+}
+
+// Dense VALU check of an FP8 product: adds sum((C - ref)^2) to out2[0] and sum(ref^2) to out2[1]
+// (device pointer, 2 floats that the caller zeroes).
+AMDPROBE_EXPORT int amdprobe_gemm_f8_check(const void* A, const void* Bt, const float* C, int M, int N, int K,
+                                           int fmt_a, int fmt_b, const void* sa, const void* sb, int inject,
+                                           float* out2, void* stream) {
+  if (M <= 0 || N <= 0 || K <= 0 || M % CHECK_TILE || N % CHECK_TILE || K % 32 || K > F8_CHECK_MAX_K)
+    return ERR_SHAPE;
+  if ((sa == nullptr) != (sb == nullptr)) return ERR_SHAPE;
+  if (!aligned16(A) || !aligned16(Bt)) return ERR_ALIGN;
+  const dim3 grid((M / CHECK_TILE) * (N / CHECK_TILE)), block(CHECK_THREADS);
+  const uint8_t *a = (const uint8_t*)A, *b = (const uint8_t*)Bt, *pa = (const uint8_t*)sa, *pb = (const uint8_t*)sb;
+  hipStream_t s = (hipStream_t)stream;
+  if (fmt_a == F8_E4M3 && fmt_b == F8_E4M3)
+    hipLaunchKernelGGL((gemm_f8_check_kernel<F8_E4M3, F8_E4M3>), grid, block, 0, s, a, b, C, pa, pb, M, N, K, inject,
+                       out2);
+  else if (fmt_a == F8_E5M2 && fmt_b == F8_E5M2)
+    hipLaunchKernelGGL((gemm_f8_check_kernel<F8_E5M2, F8_E5M2>), grid, block, 0, s, a, b, C, pa, pb, M, N, K, inject,
+                       out2);
+  else if (fmt_a == F8_E4M3 && fmt_b == F8_E5M2)
+    hipLaunchKernelGGL((gemm_f8_check_kernel<F8_E4M3, F8_E5M2>), grid, block, 0, s, a, b, C, pa, pb, M, N, K, inject,
+                       out2);
+  else
+    return ERR_SHAPE;
+  return (int)hipGetLastError();
+}
+
+// The readiness operand fill on its own: kind 0 = E4M3 bytes, 1 = E5M2 bytes, 2 = E8M0 block
+// scales (see f8_fill_kernel). `zero2` (2 floats) may be null.
+AMDPROBE_EXPORT int amdprobe_f8_fill(void* p, size_t bytes, unsigned seed, int kind, float* zero2, void* stream) {
+  if (bytes == 0 || bytes % 16 || kind < F8_FILL_E4M3 || kind > F8_FILL_SCALE) return ERR_SHAPE;
+  if (!aligned16(p)) return ERR_ALIGN;
+  static const uint32_t and4[3] = {0x87878787u, 0x83838383u, 0x07070707u};
+  static const uint32_t add4[3] = {0x30303030u, 0x38383838u, 0x7C7C7C7Cu};
+  const int blocks = (int)((bytes / 16 + 255) / 256 < 1024 ? (bytes / 16 + 255) / 256 : 1024);
+  hipLaunchKernelGGL(f8_fill_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (uint4*)p, bytes / 16,
+                     (uint32_t)seed, and4[kind], add4[kind], zero2);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// amdprobe_readiness_f8: the FP8 matrix path of one device in one call. mode 0 = fp8 (E4M3),
+// 1 = bf8 (E5M2), 2 = mxfp8 (E4M3 with E8M0 block scales through the MFMA scale inputs). Same
+// pattern as amdprobe_readiness, on a context of its own (created on first use per device): hashed
+// operands, C poisoned with NaN bytes, the f8 GEMM, the dense VALU check, one 8-byte read-back on
+// a private stream; the call counter is mixed into the seed. inject: 0 = none, 1 = lose one 16x16
+// tile of the product, 3 = skip the GEMM launch (both must fail). There is no HBM pattern here:
+// amdprobe_readiness does that.
+// ---------------------------------------------------------------------------------------
+namespace {
+struct ReadinessF8Ctx {
+  std::mutex mu;
+  bool ready = false;
+  hipStream_t stream = nullptr;
+  uint8_t* ab = nullptr;      // A (RM x RK) then Bt (RN x RK)
+  uint8_t* scales = nullptr;  // sa (RM x RK/32) then sb (RN x RK/32)
+  float* c = nullptr;         // RM x RN
+  float* res = nullptr;       // diff2, ref2
+  float* host = nullptr;      // pinned
+  uint32_t calls = 0;
+};
+ReadinessF8Ctx g_readiness_f8[MAX_DEVICES];
+
+void readiness_f8_release(ReadinessF8Ctx& ctx) {
+  if (ctx.stream != nullptr) (void)hipStreamDestroy(ctx.stream);
+  if (ctx.ab != nullptr) (void)hipFree(ctx.ab);
+  if (ctx.scales != nullptr) (void)hipFree(ctx.scales);
+  if (ctx.c != nullptr) (void)hipFree(ctx.c);
+  if (ctx.res != nullptr) (void)hipFree(ctx.res);
+  if (ctx.host != nullptr) (void)hipHostFree(ctx.host);
+  ctx.stream = nullptr;
+  ctx.ab = ctx.scales = nullptr;
+  ctx.c = ctx.res = ctx.host = nullptr;
+}
+
+int readiness_f8_alloc(ReadinessF8Ctx& ctx) {
+  PROBE_TRY(hipStreamCreateWithFlags(&ctx.stream, hipStreamNonBlocking));
+  PROBE_TRY(hipMalloc((void**)&ctx.ab, size_t(RM + RN) * RK));
+  PROBE_TRY(hipMalloc((void**)&ctx.scales, size_t(RM + RN) * (RK / 32)));
+  PROBE_TRY(hipMalloc((void**)&ctx.c, size_t(RM) * RN * sizeof(float)));
+  PROBE_TRY(hipMalloc((void**)&ctx.res, 2 * sizeof(float)));
+  PROBE_TRY(hipHostMalloc((void**)&ctx.host, 2 * sizeof(float), hipHostMallocDefault));
+  return 0;
+}
+}  // namespace
+
+AMDPROBE_EXPORT int amdprobe_readiness_f8(int device, unsigned seed, int mode, int inject, double* rel_err) {
+  if (rel_err == nullptr || device < 0 || device >= MAX_DEVICES || mode < 0 || mode > 2) return ERR_SHAPE;
+  int ndev = 0;
+  PROBE_TRY(hipGetDeviceCount(&ndev));
+  if (device >= ndev) return ERR_SHAPE;
+  ReadinessF8Ctx& ctx = g_readiness_f8[device];
+  std::lock_guard<std::mutex> lock(ctx.mu);
+  DeviceGuard guard(device);
+  if (!ctx.ready) {
+    const int rc = readiness_f8_alloc(ctx);
+    if (rc) {
+      readiness_f8_release(ctx);
+      return rc;
+    }
+    ctx.ready = true;
+  }
+  hipStream_t s = ctx.stream;
+  const int fmt = mode == 1 ? F8_E5M2 : F8_E4M3;
+  const uint8_t* A = ctx.ab;
+  const uint8_t* Bt = ctx.ab + size_t(RM) * RK;
+  const uint8_t* sa = mode == 2 ? ctx.scales : nullptr;
+  const uint8_t* sb = mode == 2 ? ctx.scales + size_t(RM) * (RK / 32) : nullptr;
+  const uint32_t call_seed = (uint32_t)seed ^ (0x9E3779B9u * ++ctx.calls);
+  int rc = amdprobe_f8_fill(ctx.ab, size_t(RM + RN) * RK, call_seed, fmt == F8_E5M2 ? F8_FILL_E5M2 : F8_FILL_E4M3,
+                            ctx.res, s);
+  if (rc) return rc;
+  if (mode == 2) {
+    rc = amdprobe_f8_fill(ctx.scales, size_t(RM + RN) * (RK / 32), call_seed ^ 0x5CA1E5u, F8_FILL_SCALE, nullptr, s);
+    if (rc) return rc;
+  }
+  PROBE_TRY(hipMemsetAsync(ctx.c, 0xFF, size_t(RM) * RN * sizeof(float), s));  // NaN until the GEMM writes
+  if (inject != 3) {
+    rc = amdprobe_gemm_f8_nt(A, Bt, ctx.c, RM, RN, RK, fmt, fmt, sa, sb, s);
+    if (rc) return rc;
+  }
+  rc = amdprobe_gemm_f8_check(A, Bt, ctx.c, RM, RN, RK, fmt, fmt, sa, sb, inject == 1 ? 1 : 0, ctx.res, s);
+  if (rc) return rc;
+  PROBE_TRY(hipMemcpyAsync(ctx.host, ctx.res, 2 * sizeof(float), hipMemcpyDeviceToHost, s));
+  PROBE_TRY(hipStreamSynchronize(s));
+  const double d2 = ctx.host[0], w2 = ctx.host[1];
+  *rel_err = (w2 > 0.0 && std::isfinite(d2)) ? std::sqrt(d2 / w2) : HUGE_VAL;  // NaN C (never written) fails
   return 0;
 }

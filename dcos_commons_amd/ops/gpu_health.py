@@ -7,6 +7,10 @@ Runs the HIP probe kernels on one device and decides healthy / unhealthy:
   probe compares with a dense fp32 matmul, the readiness probe with an fp32 VALU reference of
   every element computed on the device (``ops.readiness``, one native call). Relative error
   must stay < 1e-3;
+* **FP8 / MXFP8 MFMA numerics** (opt-in, ``matrix=`` / ``--matrix``) -- the f8f6f4 matrix path and
+  its E8M0 block-scale inputs, which the bf16 check never touches: ``ops.readiness_f8`` runs the
+  f8 GEMM on hashed operands against a VALU reference of every element, per mode ``fp8`` (E4M3),
+  ``bf8`` (E5M2), ``mxfp8`` (E4M3 with block scales). Same < 1e-3 bound;
 * **MFMA rate** -- register-resident ``v_mfma_f32_32x32x16_bf16`` loop (TFLOP/s);
 * **HBM** -- 16-B/lane streaming copy of a buffer larger than the 256 MiB Infinity Cache
   (read+write GB/s) and an address-hashed write/verify pattern (bad words must be 0).
@@ -24,22 +28,38 @@ import time
 MIN_TFLOPS = 200.0       # far below the ~2.5 PF dense peak: catches a broken/throttled matrix pipe
 MIN_HBM_GBPS = 1000.0    # far below the ~5.5 TB/s measured copy rate: catches a degraded stack
 MAX_GEMM_REL_ERR = 1e-3
+MATRIX_MODES = ("bf16", "fp8", "bf8", "mxfp8")   # bf16 is always checked; the rest are opt-in
 
 
-def readiness_probe(device: int = 0) -> dict:
+def _f8_modes(matrix) -> list:
+    unknown = [m for m in matrix if m not in MATRIX_MODES]
+    if unknown:
+        raise ValueError(f"unknown matrix mode(s) {unknown}: {list(MATRIX_MODES)}")
+    return [m for m in MATRIX_MODES[1:] if m in matrix]
+
+
+def readiness_probe(device: int = 0, matrix=("bf16",)) -> dict:
     """The fast form used as a pod readiness check: numerics + memory integrity only, as ONE
     native call (``ops.readiness``): hashed bf16 operands, the MFMA GEMM, a dense fp32 check of
     every product element and the 64 MiB pattern test on a private stream with a single read-back. It sits on the deploy and
-    recovery critical path of every GPU pod, and the GIL is released while it runs."""
+    recovery critical path of every GPU pod, and the GIL is released while it runs. Each of ``fp8``, ``bf8``,
+    ``mxfp8`` in ``matrix`` adds one ``ops.readiness_f8`` call and a ``gemm_<mode>_rel_err`` field."""
     from dcos_commons_amd import ops
 
     t0 = time.perf_counter()
     rel, bad = ops.readiness(device, seed=4321 + device)
-    return {"device": device, "gemm_rel_err": rel, "mem_bad_words": bad,
-            "healthy": bool(rel < MAX_GEMM_REL_ERR and bad == 0), "probe_seconds": round(time.perf_counter() - t0, 4)}
+    rep = {"device": device, "gemm_rel_err": rel, "mem_bad_words": bad}
+    healthy = rel < MAX_GEMM_REL_ERR and bad == 0
+    for mode in _f8_modes(matrix):
+        rel8 = ops.readiness_f8(device, seed=4321 + device, mode=mode)
+        rep[f"gemm_{mode}_rel_err"] = rel8
+        healthy = healthy and rel8 < MAX_GEMM_REL_ERR
+    rep["healthy"] = bool(healthy)
+    rep["probe_seconds"] = round(time.perf_counter() - t0, 4)
+    return rep
 
 
-def run_probe(device: int = 0, quick: bool = True) -> dict:
+def run_probe(device: int = 0, quick: bool = True, matrix=("bf16",)) -> dict:
     import torch
 
     from dcos_commons_amd import ops
@@ -77,6 +97,30 @@ def run_probe(device: int = 0, quick: bool = True) -> dict:
     e1.record()
     e1.synchronize()
     report["gemm_tflops"] = round(2.0 * s * s * s * reps / (e0.elapsed_time(e1) / 1e3) / 1e12, 1)
+    f8_ok = True
+    for mode in _f8_modes(matrix):
+        # numerics through the native check (hashed operands), throughput on the same square shape
+        rel8 = ops.readiness_f8(device, seed=1234 + device, mode=mode)
+        report[f"gemm_{mode}_rel_err"] = rel8
+        f8_ok = f8_ok and rel8 < MAX_GEMM_REL_ERR
+        dt = torch.float8_e5m2 if mode == "bf8" else torch.float8_e4m3fn
+        ab8 = torch.empty((2 * s, s), dtype=torch.uint8, device=dev)
+        ops.f8_fill(ab8, seed=1234 + device, kind="e5m2" if mode == "bf8" else "e4m3")
+        a8, b8 = ab8[:s].view(dt), ab8[s:].view(dt)
+        sc = None
+        if mode == "mxfp8":
+            sc = torch.empty((2 * s, s // 32), dtype=torch.uint8, device=dev)
+            ops.f8_fill(sc, seed=4321 + device, kind="scale")
+        run8 = (lambda: ops.gemm_f8_nt(a8, b8, sc[:s], sc[s:], out=out)) if sc is not None else \
+            (lambda: ops.gemm_f8_nt(a8, b8, out=out))
+        run8()
+        e0.record()
+        for _ in range(reps):
+            run8()
+        e1.record()
+        e1.synchronize()
+        report[f"gemm_{mode}_tflops"] = round(2.0 * s * s * s * reps / (e0.elapsed_time(e1) / 1e3) / 1e12, 1)
+        del ab8, a8, b8, sc
     del a2, b2, out
 
     # 2. MFMA issue rate
@@ -105,7 +149,7 @@ def run_probe(device: int = 0, quick: bool = True) -> dict:
     del src, dst
     torch.cuda.synchronize(dev)
 
-    report["healthy"] = bool(rel < MAX_GEMM_REL_ERR and bad == 0 and report["mfma_tflops"] > MIN_TFLOPS and
+    report["healthy"] = bool(rel < MAX_GEMM_REL_ERR and f8_ok and bad == 0 and report["mfma_tflops"] > MIN_TFLOPS and
                              report["hbm_copy_gbps"] > MIN_HBM_GBPS)
     report["probe_seconds"] = round(time.perf_counter() - t_start, 3)
     return report
@@ -116,9 +160,13 @@ def main(argv=None) -> int:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--full", action="store_true", help="larger shapes (slower, more precise)")
     ap.add_argument("--readiness", action="store_true", help="fast numerics + memory check only")
+    ap.add_argument("--matrix", default="bf16", help="comma-separated matrix data paths to check: bf16 (always), "
+                    "fp8, bf8, mxfp8")
     ap.add_argument("--json", action="store_true")
     args = ap.parse_args(argv)
-    rep = readiness_probe(args.device) if args.readiness else run_probe(args.device, quick=not args.full)
+    matrix = tuple(m for m in args.matrix.split(",") if m)
+    rep = readiness_probe(args.device, matrix) if args.readiness else \
+        run_probe(args.device, quick=not args.full, matrix=matrix)
     print(json.dumps(rep) if args.json else "\n".join(f"{k}: {v}" for k, v in rep.items()))
     return 0 if rep["healthy"] else 1
 
