@@ -2,7 +2,7 @@
 
 The kernels live in ``csrc/probe_kernels.hip`` (MFMA bf16 GEMM, MFMA issue-rate loop, HBM
 streaming copy, HBM pattern test) and ``csrc/f8_kernels.hip`` (FP8 / MXFP8 MFMA GEMM and its
-dense VALU check) and are compiled for gfx950 into the in-tree
+dense VALU check) and ``csrc/f4_kernels.hip`` (FP4 / MXFP4 MFMA GEMM and its check) and are compiled for gfx950 into the in-tree
 ``_amdprobe.so`` (``python -m dcos_commons_amd.ops.build``). They back the GPU readiness/health
 check that gates pods which request ``gpus`` (``dcos_commons_amd.ops.gpu_health``).
 
@@ -63,6 +63,10 @@ def _bind(lib: ctypes.CDLL) -> None:
     lib.amdprobe_gemm_f8_check.restype = i
     lib.amdprobe_f8_fill.argtypes = [vp, sz, ctypes.c_uint, i, vp, vp]
     lib.amdprobe_f8_fill.restype = i
+    lib.amdprobe_gemm_f4_nt.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp]
+    lib.amdprobe_gemm_f4_nt.restype = i
+    lib.amdprobe_gemm_f4_check.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, vp, vp]
+    lib.amdprobe_gemm_f4_check.restype = i
     lib.amdprobe_readiness_f8.argtypes = [i, ctypes.c_uint, i, i, ctypes.POINTER(d)]
     lib.amdprobe_readiness_f8.restype = i
 
@@ -208,8 +212,10 @@ def readiness(device: int = 0, seed: int = 0, inject: int = 0):
 
 F8_TILE = 128                       # M, N and K granule of gemm_f8_nt
 F8_BLOCK = 32                       # K elements per E8M0 block scale
-F8_FILL_KINDS = {"e4m3": 0, "e5m2": 1, "scale": 2}
-READINESS_F8_MODES = {"fp8": 0, "bf8": 1, "mxfp8": 2}
+F8_FILL_KINDS = {"e4m3": 0, "e5m2": 1, "scale": 2, "e2m1": 3}
+READINESS_F8_MODES = {"fp8": 0, "bf8": 1, "mxfp8": 2, "mxfp4": 3}
+F4_TILE_MN = 256                    # M and N granule of gemm_f4_nt
+F4_TILE_K = 256                     # K granule (elements) of gemm_f4_nt
 
 
 def _f8_operands(what: str, a, bt, a_scale, bt_scale, granule: int, k_granule: int):
@@ -279,9 +285,82 @@ def gemm_f8_check(a, bt, c, a_scale=None, bt_scale=None, inject: int = 0):
     return float(o[0]), float(o[1])
 
 
+def _f4_operands(what: str, a, bt, a_scale, bt_scale, granule: int, k_granule: int, k_max=None, extra=()):
+    """Validates packed FP4 operands (and block scales) before native code sees them; returns
+    ``(a, bt, a_scale, bt_scale, m, n, k)`` with contiguous uint8 tensors. ``extra``: further ``(name, tensor)``
+    pairs (the output) that must be on the operands' GPU."""
+    import torch
+
+    packed = (torch.uint8, getattr(torch, "float4_e2m1fn_x2", torch.uint8))
+    if a.dtype not in packed or bt.dtype not in packed:
+        raise ProbeError(f"{what} expects packed E2M1 operands (uint8 or float4_e2m1fn_x2), got {a.dtype} and "
+                         f"{bt.dtype}")
+    if a.dim() != 2 or bt.dim() != 2 or a.shape[1] != bt.shape[1]:
+        raise ProbeError(f"{what} shape mismatch: {tuple(a.shape)} x {tuple(bt.shape)}^T (packed, K/2 bytes per row)")
+    m, k = a.shape[0], 2 * a.shape[1]
+    n = bt.shape[0]
+    if m % granule or n % granule or k % k_granule or m == 0 or n == 0 or k == 0 or (k_max and k > k_max):
+        raise ProbeError(f"{what} needs M,N % {granule} == 0 and K % {k_granule} == 0"
+                         f"{f' and K <= {k_max}' if k_max else ''}, got {m}x{n}x{k}")
+    if (a_scale is None) != (bt_scale is None):
+        raise ProbeError(f"{what}: block scales come in pairs (a_scale and bt_scale, or neither)")
+    if a_scale is not None:
+        for name, sc, rows in (("a_scale", a_scale, m), ("bt_scale", bt_scale, n)):
+            if sc.dtype != torch.uint8 or tuple(sc.shape) != (rows, k // F8_BLOCK):
+                raise ProbeError(f"{what}: {name} must be uint8 [{rows}, {k // F8_BLOCK}], got {sc.dtype} "
+                                 f"{tuple(sc.shape)}")
+        a_scale, bt_scale = a_scale.contiguous(), bt_scale.contiguous()
+    # last, so that a wrong shape is reported as such: every tensor on one GPU (the kernel gets raw pointers)
+    for name, t in (("a", a), ("bt", bt), ("a_scale", a_scale), ("bt_scale", bt_scale)) + tuple(extra):
+        if t is not None and (t.device.type != "cuda" or t.device != a.device):
+            raise ProbeError(f"{what}: {name} is on {t.device}; all operands must be on one GPU (a is on {a.device})")
+    return a.contiguous().view(torch.uint8), bt.contiguous().view(torch.uint8), a_scale, bt_scale, m, n, k
+
+
+def gemm_f4_nt(a, bt, a_scale=None, bt_scale=None, out=None):
+    """``a[M,K] @ bt[N,K]^T`` in fp32 on the FP4 MFMA kernel (``v_mfma_[scale_]f32_16x16x128_f8f6f4`` with
+    ``cbsz:4 blgp:4``); M, N % 256 == 0, K % 256 == 0. ``a`` / ``bt`` are packed OCP E2M1, ``[rows, K/2]``
+    ``uint8`` or ``float4_e2m1fn_x2`` (element ``2j`` in bits 3:0 of byte ``j``). With ``a_scale[M, K/32]`` and
+    ``bt_scale[N, K/32]`` (uint8 E8M0) the product is MXFP4, block-scaled by the instruction's scale inputs."""
+    import torch
+
+    a, bt, a_scale, bt_scale, m, n, k = _f4_operands("gemm_f4_nt", a, bt, a_scale, bt_scale, F4_TILE_MN, F4_TILE_K,
+                                                     extra=(("out", out),))
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.float32, device=a.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (m, n) or not out.is_contiguous():
+        raise ProbeError(f"gemm_f4_nt: out must be a contiguous float32 {(m, n)}, got {out.dtype} {tuple(out.shape)}")
+    sa = a_scale.data_ptr() if a_scale is not None else None
+    sb = bt_scale.data_ptr() if bt_scale is not None else None
+    _check(lib().amdprobe_gemm_f4_nt(a.data_ptr(), bt.data_ptr(), out.data_ptr(), m, n, k, sa, sb,
+                                     _stream(a.device)), "gemm_f4_nt")
+    return out
+
+
+def gemm_f4_check(a, bt, c, a_scale=None, bt_scale=None, inject: int = 0):
+    """Dense check of an FP4 (or MXFP4) product ``c`` on the GPU, every element against an fp32 VALU
+    reference decoded with integer arithmetic: returns ``(sum((c - ref)^2), sum(ref^2))``.
+    M, N % 16 == 0, K % 32 == 0, K <= 1024."""
+    import torch
+
+    a, bt, a_scale, bt_scale, m, n, k = _f4_operands("gemm_f4_check", a, bt, a_scale, bt_scale, 16, F8_BLOCK, 1024,
+                                                     extra=(("c", c),))
+    if c.dtype != torch.float32 or tuple(c.shape) != (m, n):
+        raise ProbeError(f"gemm_f4_check: c must be float32 {(m, n)}, got {c.dtype} {tuple(c.shape)}")
+    c = c.contiguous()
+    out = torch.zeros(4, dtype=torch.float32, device=a.device)
+    sa = a_scale.data_ptr() if a_scale is not None else None
+    sb = bt_scale.data_ptr() if bt_scale is not None else None
+    _check(lib().amdprobe_gemm_f4_check(a.data_ptr(), bt.data_ptr(), c.data_ptr(), m, n, k, sa, sb, inject,
+                                        out.data_ptr(), _stream(a.device)), "gemm_f4_check")
+    o = out.cpu()
+    return float(o[0]), float(o[1])
+
+
 def f8_fill(buf, seed: int, kind: str = "e4m3"):
-    """The FP8 readiness operand fill into ``buf`` (byte size % 16): finite hashed ``e4m3`` / ``e5m2``
-    bytes with |x| in [0.5, 1), or E8M0 block ``scale`` bytes in [124, 131]."""
+    """The FP8 / FP4 readiness operand fill into ``buf`` (byte size % 16): finite hashed ``e4m3`` / ``e5m2``
+    bytes with |x| in [0.5, 1), E8M0 block ``scale`` bytes in [124, 131], or ``e2m1``: any byte, two finite
+    FP4 codes."""
     if kind not in F8_FILL_KINDS:
         raise ProbeError(f"unknown f8 fill {kind!r}: {sorted(F8_FILL_KINDS)}")
     _check(lib().amdprobe_f8_fill(buf.data_ptr(), buf.numel() * buf.element_size(), seed & 0xFFFFFFFF,
@@ -290,7 +369,8 @@ def f8_fill(buf, seed: int, kind: str = "e4m3"):
 
 def readiness_f8(device: int = 0, seed: int = 0, mode: str = "fp8", inject: int = 0) -> float:
     """The FP8 matrix path of one device in one native call: hashed operands, the f8 MFMA GEMM (``fp8`` =
-    E4M3, ``bf8`` = E5M2, ``mxfp8`` = E4M3 with E8M0 block scales through the MFMA scale inputs), the dense
+    E4M3, ``bf8`` = E5M2, ``mxfp8`` = E4M3 with E8M0 block scales through the MFMA scale inputs; ``mxfp4`` = packed E2M1 with
+    block scales on the f4 GEMM), the dense
     VALU check of every element, one read-back on a private stream. Returns ``gemm_rel_err``. ``inject`` = 1
     loses a product tile, 3 skips the GEMM (tests). The GIL is released for the duration (ctypes)."""
     if mode not in READINESS_F8_MODES:

@@ -4,6 +4,7 @@
 // negative code for a rejected shape.
 #include "probe_kernels.hip"
 #include "f8_kernels.hip"
+#include "f4_kernels.hip"
 
 #include <cmath>
 #include <mutex>
@@ -295,12 +296,12 @@ AMDPROBE_EXPORT int amdprobe_gemm_f8_check(const void* A, const void* Bt, const 
 }
 
 // The readiness operand fill on its own: kind 0 = E4M3 bytes, 1 = E5M2 bytes, 2 = E8M0 block
-// scales (see f8_fill_kernel). `zero2` (2 floats) may be null.
+// scales (see f8_fill_kernel), 3 = packed E2M1 nibbles (any byte). `zero2` (2 floats) may be null.
 AMDPROBE_EXPORT int amdprobe_f8_fill(void* p, size_t bytes, unsigned seed, int kind, float* zero2, void* stream) {
-  if (bytes == 0 || bytes % 16 || kind < F8_FILL_E4M3 || kind > F8_FILL_SCALE) return ERR_SHAPE;
+  if (bytes == 0 || bytes % 16 || kind < F8_FILL_E4M3 || kind > F4_FILL_E2M1) return ERR_SHAPE;
   if (!aligned16(p)) return ERR_ALIGN;
-  static const uint32_t and4[3] = {0x87878787u, 0x83838383u, 0x07070707u};
-  static const uint32_t add4[3] = {0x30303030u, 0x38383838u, 0x7C7C7C7Cu};
+  static const uint32_t and4[4] = {0x87878787u, 0x83838383u, 0x07070707u, 0xFFFFFFFFu};
+  static const uint32_t add4[4] = {0x30303030u, 0x38383838u, 0x7C7C7C7Cu, 0u};
   const int blocks = (int)((bytes / 16 + 255) / 256 < 1024 ? (bytes / 16 + 255) / 256 : 1024);
   hipLaunchKernelGGL(f8_fill_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (uint4*)p, bytes / 16,
                      (uint32_t)seed, and4[kind], add4[kind], zero2);
@@ -308,8 +309,41 @@ AMDPROBE_EXPORT int amdprobe_f8_fill(void* p, size_t bytes, unsigned seed, int k
 }
 
 // ---------------------------------------------------------------------------------------
+// FP4 / MXFP4 (f4_kernels.hip). A, Bt: packed E2M1, K/2 bytes per row. sa / sb: E8M0 block scales
+// [M][K/32], [N][K/32], both null for an unscaled product.
+// ---------------------------------------------------------------------------------------
+AMDPROBE_EXPORT int amdprobe_gemm_f4_nt(const void* A, const void* Bt, float* C, int M, int N, int K, const void* sa,
+                                        const void* sb, void* stream) {
+  if (M <= 0 || N <= 0 || K <= 0 || M % f4::BM || N % f4::BN || K % f4::BK) return ERR_SHAPE;
+  if ((sa == nullptr) != (sb == nullptr)) return ERR_SHAPE;
+  if (!aligned16(A) || !aligned16(Bt) || !aligned16(C) || !aligned16(sa) || !aligned16(sb)) return ERR_ALIGN;
+  const dim3 grid((M / f4::BM) * (N / f4::BN)), block(f4::THREADS);
+  const uint8_t *a = (const uint8_t*)A, *b = (const uint8_t*)Bt, *pa = (const uint8_t*)sa, *pb = (const uint8_t*)sb;
+  if (sa != nullptr)
+    hipLaunchKernelGGL(gemm_f4_nt_kernel<true>, grid, block, 0, (hipStream_t)stream, a, b, C, pa, pb, M, N, K);
+  else
+    hipLaunchKernelGGL(gemm_f4_nt_kernel<false>, grid, block, 0, (hipStream_t)stream, a, b, C, pa, pb, M, N, K);
+  return (int)hipGetLastError();
+}
+
+// Dense VALU check of an FP4 product: adds sum((C - ref)^2) to out2[0] and sum(ref^2) to out2[1]
+// (device pointer, 2 floats that the caller zeroes).
+AMDPROBE_EXPORT int amdprobe_gemm_f4_check(const void* A, const void* Bt, const float* C, int M, int N, int K,
+                                           const void* sa, const void* sb, int inject, float* out2, void* stream) {
+  if (M <= 0 || N <= 0 || K <= 0 || M % CHECK_TILE || N % CHECK_TILE || K % 32 || K > F4_CHECK_MAX_K)
+    return ERR_SHAPE;
+  if ((sa == nullptr) != (sb == nullptr)) return ERR_SHAPE;
+  if (!aligned16(A) || !aligned16(Bt)) return ERR_ALIGN;
+  hipLaunchKernelGGL(gemm_f4_check_kernel, dim3((M / CHECK_TILE) * (N / CHECK_TILE)), dim3(CHECK_THREADS), 0,
+                     (hipStream_t)stream, (const uint8_t*)A, (const uint8_t*)Bt, C, (const uint8_t*)sa,
+                     (const uint8_t*)sb, M, N, K, inject, out2);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
 // amdprobe_readiness_f8: the FP8 matrix path of one device in one call. mode 0 = fp8 (E4M3),
-// 1 = bf8 (E5M2), 2 = mxfp8 (E4M3 with E8M0 block scales through the MFMA scale inputs). Same
+// 1 = bf8 (E5M2), 2 = mxfp8 (E4M3 with E8M0 block scales through the MFMA scale inputs), 3 = mxfp4
+// (packed E2M1 with block scales: the f4 GEMM and check on the same buffers, half filled). Same
 // pattern as amdprobe_readiness, on a context of its own (created on first use per device): hashed
 // operands, C poisoned with NaN bytes, the f8 GEMM, the dense VALU check, one 8-byte read-back on
 // a private stream; the call counter is mixed into the seed. inject: 0 = none, 1 = lose one 16x16
@@ -354,7 +388,7 @@ int readiness_f8_alloc(ReadinessF8Ctx& ctx) {
 }  // namespace
 
 AMDPROBE_EXPORT int amdprobe_readiness_f8(int device, unsigned seed, int mode, int inject, double* rel_err) {
-  if (rel_err == nullptr || device < 0 || device >= MAX_DEVICES || mode < 0 || mode > 2) return ERR_SHAPE;
+  if (rel_err == nullptr || device < 0 || device >= MAX_DEVICES || mode < 0 || mode > 3) return ERR_SHAPE;
   int ndev = 0;
   PROBE_TRY(hipGetDeviceCount(&ndev));
   if (device >= ndev) return ERR_SHAPE;
@@ -370,25 +404,29 @@ AMDPROBE_EXPORT int amdprobe_readiness_f8(int device, unsigned seed, int mode, i
     ctx.ready = true;
   }
   hipStream_t s = ctx.stream;
+  const bool f4 = mode == 3, mx = mode >= 2;
   const int fmt = mode == 1 ? F8_E5M2 : F8_E4M3;
+  const size_t row_bytes = f4 ? RK / 2 : RK;
   const uint8_t* A = ctx.ab;
-  const uint8_t* Bt = ctx.ab + size_t(RM) * RK;
-  const uint8_t* sa = mode == 2 ? ctx.scales : nullptr;
-  const uint8_t* sb = mode == 2 ? ctx.scales + size_t(RM) * (RK / 32) : nullptr;
+  const uint8_t* Bt = ctx.ab + size_t(RM) * row_bytes;
+  const uint8_t* sa = mx ? ctx.scales : nullptr;
+  const uint8_t* sb = mx ? ctx.scales + size_t(RM) * (RK / 32) : nullptr;
   const uint32_t call_seed = (uint32_t)seed ^ (0x9E3779B9u * ++ctx.calls);
-  int rc = amdprobe_f8_fill(ctx.ab, size_t(RM + RN) * RK, call_seed, fmt == F8_E5M2 ? F8_FILL_E5M2 : F8_FILL_E4M3,
-                            ctx.res, s);
+  int rc = amdprobe_f8_fill(ctx.ab, size_t(RM + RN) * row_bytes, call_seed,
+                            f4 ? F4_FILL_E2M1 : fmt == F8_E5M2 ? F8_FILL_E5M2 : F8_FILL_E4M3, ctx.res, s);
   if (rc) return rc;
-  if (mode == 2) {
+  if (mx) {
     rc = amdprobe_f8_fill(ctx.scales, size_t(RM + RN) * (RK / 32), call_seed ^ 0x5CA1E5u, F8_FILL_SCALE, nullptr, s);
     if (rc) return rc;
   }
   PROBE_TRY(hipMemsetAsync(ctx.c, 0xFF, size_t(RM) * RN * sizeof(float), s));  // NaN until the GEMM writes
   if (inject != 3) {
-    rc = amdprobe_gemm_f8_nt(A, Bt, ctx.c, RM, RN, RK, fmt, fmt, sa, sb, s);
+    rc = f4 ? amdprobe_gemm_f4_nt(A, Bt, ctx.c, RM, RN, RK, sa, sb, s)
+            : amdprobe_gemm_f8_nt(A, Bt, ctx.c, RM, RN, RK, fmt, fmt, sa, sb, s);
     if (rc) return rc;
   }
-  rc = amdprobe_gemm_f8_check(A, Bt, ctx.c, RM, RN, RK, fmt, fmt, sa, sb, inject == 1 ? 1 : 0, ctx.res, s);
+  rc = f4 ? amdprobe_gemm_f4_check(A, Bt, ctx.c, RM, RN, RK, sa, sb, inject == 1 ? 1 : 0, ctx.res, s)
+          : amdprobe_gemm_f8_check(A, Bt, ctx.c, RM, RN, RK, fmt, fmt, sa, sb, inject == 1 ? 1 : 0, ctx.res, s);
   if (rc) return rc;
   PROBE_TRY(hipMemcpyAsync(ctx.host, ctx.res, 2 * sizeof(float), hipMemcpyDeviceToHost, s));
   PROBE_TRY(hipStreamSynchronize(s));
