@@ -1,10 +1,15 @@
 """MI355X device ops: HIP probe kernels behind a torch-tensor API.
 
-The kernels live in ``csrc/probe_kernels.hip`` (MFMA bf16 GEMM, MFMA issue-rate loop, HBM
-streaming copy, HBM pattern test) and ``csrc/f8_kernels.hip`` (FP8 / MXFP8 MFMA GEMM and its
-dense VALU check) and ``csrc/f4_kernels.hip`` (FP4 / MXFP4 MFMA GEMM and its check) and are compiled for gfx950 into the in-tree
-``_amdprobe.so`` (``python -m dcos_commons_amd.ops.build``). They back the GPU readiness/health
-check that gates pods which request ``gpus`` (``dcos_commons_amd.ops.gpu_health``).
+The kernels live in three files under ``csrc/``:
+
+* ``probe_kernels.hip``: MFMA bf16 GEMM, MFMA issue-rate loop, HBM streaming copy, HBM pattern test,
+  the hashed operand fill and the shared parts of the dense VALU check;
+* ``f8_kernels.hip``: FP8 / MXFP8 MFMA GEMM and its check;
+* ``f4_kernels.hip``: FP4 / MXFP4 MFMA GEMM and its check.
+
+They are compiled for gfx950 into the in-tree ``_amdprobe.so`` (``python -m dcos_commons_amd.ops.build``)
+and back the GPU readiness/health check that gates pods which request ``gpus``
+(``dcos_commons_amd.ops.gpu_health``).
 
 There is deliberately no PyTorch fallback: on a machine with a GPU, a missing or stale
 extension raises ``ProbeUnavailable`` instead of silently running something else.
@@ -35,40 +40,31 @@ class ProbeError(RuntimeError):
 
 
 def _bind(lib: ctypes.CDLL) -> None:
-    vp, i, sz, f, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float, ctypes.c_double
-    lib.amdprobe_version.restype = i
-    lib.amdprobe_gemm_bf16_nt.argtypes = [vp, vp, vp, i, i, i, vp]
-    lib.amdprobe_gemm_bf16_nt.restype = i
-    lib.amdprobe_gemm_bf16_nt_variant.argtypes = [vp, vp, vp, i, i, i, i, vp]
-    lib.amdprobe_gemm_bf16_nt_variant.restype = i
-    lib.amdprobe_mfma_peak.argtypes = [vp, i, i, f, vp]
-    lib.amdprobe_mfma_peak.restype = i
-    lib.amdprobe_mfma_peak_flops.argtypes = [i, i]
-    lib.amdprobe_mfma_peak_flops.restype = d
-    lib.amdprobe_hbm_copy.argtypes = [vp, vp, sz, i, vp]
-    lib.amdprobe_hbm_copy.restype = i
-    lib.amdprobe_pattern_write.argtypes = [vp, sz, ctypes.c_uint, i, vp]
-    lib.amdprobe_pattern_write.restype = i
-    lib.amdprobe_pattern_check.argtypes = [vp, sz, ctypes.c_uint, vp, i, vp]
-    lib.amdprobe_pattern_check.restype = i
-    lib.amdprobe_gemm_check.argtypes = [vp, vp, vp, i, i, i, i, vp, vp]
-    lib.amdprobe_gemm_check.restype = i
-    lib.amdprobe_readiness_fill.argtypes = [vp, sz, ctypes.c_uint, vp, vp]
-    lib.amdprobe_readiness_fill.restype = i
-    lib.amdprobe_readiness.argtypes = [i, ctypes.c_uint, i, ctypes.POINTER(d), ctypes.POINTER(ctypes.c_ulonglong)]
-    lib.amdprobe_readiness.restype = i
-    lib.amdprobe_gemm_f8_nt.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp, vp]
-    lib.amdprobe_gemm_f8_nt.restype = i
-    lib.amdprobe_gemm_f8_check.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp, i, vp, vp]
-    lib.amdprobe_gemm_f8_check.restype = i
-    lib.amdprobe_f8_fill.argtypes = [vp, sz, ctypes.c_uint, i, vp, vp]
-    lib.amdprobe_f8_fill.restype = i
-    lib.amdprobe_gemm_f4_nt.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp]
-    lib.amdprobe_gemm_f4_nt.restype = i
-    lib.amdprobe_gemm_f4_check.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, vp, vp]
-    lib.amdprobe_gemm_f4_check.restype = i
-    lib.amdprobe_readiness_f8.argtypes = [i, ctypes.c_uint, i, i, ctypes.POINTER(d)]
-    lib.amdprobe_readiness_f8.restype = i
+    vp, i, u, sz, f, d = (ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_size_t, ctypes.c_float,
+                          ctypes.c_double)
+    pd, pull = ctypes.POINTER(d), ctypes.POINTER(ctypes.c_ulonglong)
+    for name, restype, argtypes in (
+            ("version", i, None),
+            ("gemm_bf16_nt", i, [vp, vp, vp, i, i, i, vp]),
+            ("gemm_bf16_nt_variant", i, [vp, vp, vp, i, i, i, i, vp]),
+            ("mfma_peak", i, [vp, i, i, f, vp]),
+            ("mfma_peak_flops", d, [i, i]),
+            ("hbm_copy", i, [vp, vp, sz, i, vp]),
+            ("pattern_write", i, [vp, sz, u, i, vp]),
+            ("pattern_check", i, [vp, sz, u, vp, i, vp]),
+            ("gemm_check", i, [vp, vp, vp, i, i, i, i, vp, vp]),
+            ("readiness_fill", i, [vp, sz, u, vp, vp]),
+            ("readiness", i, [i, u, i, pd, pull]),
+            ("gemm_f8_nt", i, [vp, vp, vp, i, i, i, i, i, vp, vp, vp]),
+            ("gemm_f8_check", i, [vp, vp, vp, i, i, i, i, i, vp, vp, i, vp, vp]),
+            ("f8_fill", i, [vp, sz, u, i, vp, vp]),
+            ("gemm_f4_nt", i, [vp, vp, vp, i, i, i, vp, vp, vp]),
+            ("gemm_f4_check", i, [vp, vp, vp, i, i, i, vp, vp, i, vp, vp]),
+            ("readiness_f8", i, [i, u, i, i, pd])):
+        fn = getattr(lib, "amdprobe_" + name)
+        fn.restype = restype
+        if argtypes is not None:
+            fn.argtypes = argtypes
 
 
 def lib() -> ctypes.CDLL:
@@ -99,6 +95,91 @@ def _check(rc: int, what: str) -> None:
         raise ProbeError(f"{what}: HIP error {rc}")
 
 
+F8_TILE = 128                       # M, N and K granule of gemm_f8_nt
+F8_BLOCK = 32                       # K elements per E8M0 block scale
+F8_FILL_KINDS = {"e4m3": 0, "e5m2": 1, "scale": 2, "e2m1": 3}
+READINESS_F8_MODES = {"fp8": 0, "bf8": 1, "mxfp8": 2, "mxfp4": 3}
+F4_TILE_MN = 256                    # M and N granule of gemm_f4_nt
+F4_TILE_K = 256                     # K granule (elements) of gemm_f4_nt
+_CHECK_TILE = 16                    # M and N granule of the dense checks
+_CHECK_MAX_K = 1024                 # their largest K (one tile's operand rows sit in LDS)
+
+
+def _operands(what: str, kind: str, a, bt, granule: int, k_granule: int, k_max=None, a_scale=None, bt_scale=None,
+              out=None, c=None):
+    """Validates the operands of a GEMM or check wrapper before native code sees their pointers; returns
+    ``(a, bt, a_scale, bt_scale, res, m, n, k, fmt)`` with contiguous tensors. ``kind`` is ``bf16``, ``fp8``
+    (``fmt`` = the two format codes of the native call, else ``()``) or ``fp4`` (packed: K is twice the row
+    length; the operands come back as uint8). ``res`` is the product: ``c`` made contiguous when the caller
+    has one to check, else ``out``, allocated when ``None``. Shape, granule, dtype and paired-scale errors
+    are reported first; then every tensor must be on the operands' one GPU, and the product a float32
+    ``(m, n)``, a caller's ``out`` contiguous as well (the kernel writes through its pointer)."""
+    import torch
+
+    fmt = ()
+    if kind == "bf16":
+        ok, expects = a.dtype == bt.dtype == torch.bfloat16, "bfloat16"
+    elif kind == "fp8":
+        codes = {torch.float8_e4m3fn: 0, torch.float8_e5m2: 1}
+        ok, expects = a.dtype in codes and bt.dtype in codes, "float8_e4m3fn / float8_e5m2"
+        if ok:
+            fmt = (codes[a.dtype], codes[bt.dtype])
+            if fmt == (1, 0):
+                raise ProbeError(f"{what}: E5M2 x E4M3 is not built (swap the operands: E4M3 x E5M2 is)")
+    else:
+        packed = (torch.uint8, getattr(torch, "float4_e2m1fn_x2", torch.uint8))
+        ok, expects = a.dtype in packed and bt.dtype in packed, "packed E2M1 (uint8 or float4_e2m1fn_x2)"
+    if not ok:
+        raise ProbeError(f"{what} expects {expects} operands, got {a.dtype} and {bt.dtype}")
+    if a.dim() != 2 or bt.dim() != 2 or a.shape[1] != bt.shape[1]:
+        raise ProbeError(f"{what} shape mismatch: {tuple(a.shape)} x {tuple(bt.shape)}^T"
+                         f"{' (packed, K/2 bytes per row)' if kind == 'fp4' else ''}")
+    m, n, k = a.shape[0], bt.shape[0], a.shape[1] * (2 if kind == "fp4" else 1)
+    if m % granule or n % granule or k % k_granule or m == 0 or n == 0 or k == 0 or (k_max and k > k_max):
+        raise ProbeError(f"{what} needs M,N % {granule} == 0 and K % {k_granule} == 0"
+                         f"{f' and K <= {k_max}' if k_max else ''}, got {m}x{n}x{k}")
+    if (a_scale is None) != (bt_scale is None):
+        raise ProbeError(f"{what}: block scales come in pairs (a_scale and bt_scale, or neither)")
+    if a_scale is not None:
+        for name, sc, rows in (("a_scale", a_scale, m), ("bt_scale", bt_scale, n)):
+            if sc.dtype != torch.uint8 or tuple(sc.shape) != (rows, k // F8_BLOCK):
+                raise ProbeError(f"{what}: {name} must be uint8 [{rows}, {k // F8_BLOCK}], got {sc.dtype} "
+                                 f"{tuple(sc.shape)}")
+        a_scale, bt_scale = a_scale.contiguous(), bt_scale.contiguous()
+    # last, so that a wrong shape is reported as such: every tensor on one GPU (the kernel gets raw pointers)
+    for name, t in (("a", a), ("bt", bt), ("a_scale", a_scale), ("bt_scale", bt_scale), ("out", out), ("c", c)):
+        if t is not None and (t.device.type != "cuda" or t.device != a.device):
+            raise ProbeError(f"{what}: {name} is on {t.device}; all operands must be on one GPU (a is on {a.device})")
+    for name, t in (("out", out), ("c", c)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (m, n) or
+                              (t is out and not t.is_contiguous())):
+            raise ProbeError(f"{what}: {name} must be a{' contiguous' if t is out else ''} float32 {(m, n)}, got "
+                             f"{t.dtype} {tuple(t.shape)} with strides {t.stride()}")
+    if c is not None:
+        res = c.contiguous()
+    else:
+        res = out if out is not None else torch.empty((m, n), dtype=torch.float32, device=a.device)
+    a, bt = a.contiguous(), bt.contiguous()
+    if kind == "fp4":
+        a, bt = a.view(torch.uint8), bt.view(torch.uint8)
+    return a, bt, a_scale, bt_scale, res, m, n, k, fmt
+
+
+def _scale_ptrs(a_scale, bt_scale):
+    """The two block-scale pointers of a native call (``None`` = null: an unscaled product)."""
+    return (None, None) if a_scale is None else (a_scale.data_ptr(), bt_scale.data_ptr())
+
+
+def _run_check(what: str, fn, device, *args):
+    """Runs a dense-check entry point, ``fn(*args, out2, stream)``, on a zeroed result; returns ``(d2, w2)``."""
+    import torch
+
+    out = torch.zeros(4, dtype=torch.float32, device=device)
+    _check(fn(*args, out.data_ptr(), _stream(device)), what)
+    o = out.cpu()
+    return float(o[0]), float(o[1])
+
+
 GEMM_VARIANTS = {"auto": 0, "tile128": 1, "glds256": 2}
 
 
@@ -107,21 +188,9 @@ def gemm_bf16_nt(a, bt, out=None, variant: str = "auto"):
 
     ``auto`` runs the 256x256 LDS-DMA pipelined kernel when M, N % 256 == 0 and K % 128 == 0 and
     the 128x128 register-staged kernel otherwise; ``tile128`` / ``glds256`` force one."""
-    import torch
-
-    if a.dtype != torch.bfloat16 or bt.dtype != torch.bfloat16:
-        raise ProbeError("gemm_bf16_nt expects bf16 operands")
-    if a.dim() != 2 or bt.dim() != 2 or a.shape[1] != bt.shape[1]:
-        raise ProbeError(f"gemm_bf16_nt shape mismatch: {tuple(a.shape)} x {tuple(bt.shape)}^T")
-    m, k = a.shape
-    n = bt.shape[0]
-    if m % GEMM_TILE_M or n % GEMM_TILE_N or k % GEMM_TILE_K:
-        raise ProbeError(f"gemm_bf16_nt needs M,N % 128 == 0 and K % 64 == 0, got {m}x{n}x{k}")
-    a, bt = a.contiguous(), bt.contiguous()
-    if out is None:
-        out = torch.empty((m, n), dtype=torch.float32, device=a.device)
     if variant not in GEMM_VARIANTS:
         raise ProbeError(f"unknown GEMM variant {variant!r}: {sorted(GEMM_VARIANTS)}")
+    a, bt, _, _, out, m, n, k, _ = _operands("gemm_bf16_nt", "bf16", a, bt, GEMM_TILE_M, GEMM_TILE_K, out=out)
     _check(lib().amdprobe_gemm_bf16_nt_variant(a.data_ptr(), bt.data_ptr(), out.data_ptr(), m, n, k,
                                                GEMM_VARIANTS[variant], _stream(a.device)), "gemm_bf16_nt")
     return out
@@ -169,19 +238,9 @@ def pattern_check(buf, seed: int, blocks: int = 2048) -> int:
 def gemm_check(a, bt, c, inject: int = 0):
     """Dense check of ``c == a @ bt.T`` on the GPU (an fp32 VALU reference per element): returns
     ``(sum((c - a bt^T)^2), sum((a bt^T)^2))``. M, N % 16 == 0, K % 8 == 0, K <= 1024."""
-    import torch
-
-    m, k = a.shape
-    n = bt.shape[0]
-    if a.dtype != torch.bfloat16 or bt.dtype != torch.bfloat16 or c.dtype != torch.float32 or \
-            tuple(c.shape) != (m, n) or bt.shape[1] != k:
-        raise ProbeError(f"gemm_check: bad operands {tuple(a.shape)} {tuple(bt.shape)} {tuple(c.shape)}")
-    a, bt, c = a.contiguous(), bt.contiguous(), c.contiguous()
-    out = torch.zeros(4, dtype=torch.float32, device=a.device)
-    _check(lib().amdprobe_gemm_check(a.data_ptr(), bt.data_ptr(), c.data_ptr(), m, n, k, inject, out.data_ptr(),
-                                     _stream(a.device)), "gemm_check")
-    o = out.cpu()
-    return float(o[0]), float(o[1])
+    a, bt, _, _, c, m, n, k, _ = _operands("gemm_check", "bf16", a, bt, _CHECK_TILE, 8, _CHECK_MAX_K, c=c)
+    return _run_check("gemm_check", lib().amdprobe_gemm_check, a.device, a.data_ptr(), bt.data_ptr(), c.data_ptr(),
+                      m, n, k, inject)
 
 
 def readiness_fill(ab, seed: int):
@@ -210,58 +269,16 @@ def readiness(device: int = 0, seed: int = 0, inject: int = 0):
     return rel.value, int(bad.value)
 
 
-F8_TILE = 128                       # M, N and K granule of gemm_f8_nt
-F8_BLOCK = 32                       # K elements per E8M0 block scale
-F8_FILL_KINDS = {"e4m3": 0, "e5m2": 1, "scale": 2, "e2m1": 3}
-READINESS_F8_MODES = {"fp8": 0, "bf8": 1, "mxfp8": 2, "mxfp4": 3}
-F4_TILE_MN = 256                    # M and N granule of gemm_f4_nt
-F4_TILE_K = 256                     # K granule (elements) of gemm_f4_nt
-
-
-def _f8_operands(what: str, a, bt, a_scale, bt_scale, granule: int, k_granule: int):
-    """Validates fp8 operands (and block scales) before native code sees them; returns
-    ``(a, bt, fmt_a, fmt_b, a_scale, bt_scale, m, n, k)`` with contiguous tensors."""
-    import torch
-
-    fmts = {torch.float8_e4m3fn: 0, torch.float8_e5m2: 1}
-    if a.dtype not in fmts or bt.dtype not in fmts:
-        raise ProbeError(f"{what} expects float8_e4m3fn / float8_e5m2 operands, got {a.dtype} and {bt.dtype}")
-    fa, fb = fmts[a.dtype], fmts[bt.dtype]
-    if (fa, fb) == (1, 0):
-        raise ProbeError(f"{what}: E5M2 x E4M3 is not built (swap the operands: E4M3 x E5M2 is)")
-    if a.dim() != 2 or bt.dim() != 2 or a.shape[1] != bt.shape[1]:
-        raise ProbeError(f"{what} shape mismatch: {tuple(a.shape)} x {tuple(bt.shape)}^T")
-    m, k = a.shape
-    n = bt.shape[0]
-    if m % granule or n % granule or k % k_granule:
-        raise ProbeError(f"{what} needs M,N % {granule} == 0 and K % {k_granule} == 0, got {m}x{n}x{k}")
-    if (a_scale is None) != (bt_scale is None):
-        raise ProbeError(f"{what}: block scales come in pairs (a_scale and bt_scale, or neither)")
-    if a_scale is not None:
-        for name, sc, rows in (("a_scale", a_scale, m), ("bt_scale", bt_scale, n)):
-            if sc.dtype != torch.uint8 or tuple(sc.shape) != (rows, k // F8_BLOCK):
-                raise ProbeError(f"{what}: {name} must be uint8 [{rows}, {k // F8_BLOCK}], got {sc.dtype} "
-                                 f"{tuple(sc.shape)}")
-        a_scale, bt_scale = a_scale.contiguous(), bt_scale.contiguous()
-    return a.contiguous(), bt.contiguous(), fa, fb, a_scale, bt_scale, m, n, k
-
-
 def gemm_f8_nt(a, bt, a_scale=None, bt_scale=None, out=None):
     """``a[M,K] @ bt[N,K]^T`` in fp32 on the FP8 MFMA kernel (``v_mfma_f32_16x16x128_f8f6f4``);
     M, N, K % 128 == 0. ``a`` / ``bt`` are ``float8_e4m3fn`` or ``float8_e5m2`` (E4M3 x E4M3,
     E5M2 x E5M2, E4M3 x E5M2). With ``a_scale[M, K/32]`` and ``bt_scale[N, K/32]`` (uint8 E8M0, value
     ``2^(s - 127)`` per 32 K elements) the product is MX block-scaled by the instruction's scale
     inputs (``v_mfma_scale_f32_16x16x128_f8f6f4``)."""
-    import torch
-
-    a, bt, fa, fb, a_scale, bt_scale, m, n, k = _f8_operands("gemm_f8_nt", a, bt, a_scale, bt_scale, F8_TILE,
-                                                              F8_TILE)
-    if out is None:
-        out = torch.empty((m, n), dtype=torch.float32, device=a.device)
-    sa = a_scale.data_ptr() if a_scale is not None else None
-    sb = bt_scale.data_ptr() if bt_scale is not None else None
-    _check(lib().amdprobe_gemm_f8_nt(a.data_ptr(), bt.data_ptr(), out.data_ptr(), m, n, k, fa, fb, sa, sb,
-                                     _stream(a.device)), "gemm_f8_nt")
+    a, bt, a_scale, bt_scale, out, m, n, k, fmt = _operands("gemm_f8_nt", "fp8", a, bt, F8_TILE, F8_TILE,
+                                                            a_scale=a_scale, bt_scale=bt_scale, out=out)
+    _check(lib().amdprobe_gemm_f8_nt(a.data_ptr(), bt.data_ptr(), out.data_ptr(), m, n, k, *fmt,
+                                     *_scale_ptrs(a_scale, bt_scale), _stream(a.device)), "gemm_f8_nt")
     return out
 
 
@@ -269,52 +286,10 @@ def gemm_f8_check(a, bt, c, a_scale=None, bt_scale=None, inject: int = 0):
     """Dense check of an FP8 (or MX block-scaled) product ``c`` on the GPU, every element against an
     fp32 VALU reference that never touches the matrix pipe: returns ``(sum((c - ref)^2), sum(ref^2))``.
     M, N % 16 == 0, K % 32 == 0, K <= 1024."""
-    import torch
-
-    a, bt, fa, fb, a_scale, bt_scale, m, n, k = _f8_operands("gemm_f8_check", a, bt, a_scale, bt_scale, 16,
-                                                              F8_BLOCK)
-    if c.dtype != torch.float32 or tuple(c.shape) != (m, n):
-        raise ProbeError(f"gemm_f8_check: c must be float32 {(m, n)}, got {c.dtype} {tuple(c.shape)}")
-    c = c.contiguous()
-    out = torch.zeros(4, dtype=torch.float32, device=a.device)
-    sa = a_scale.data_ptr() if a_scale is not None else None
-    sb = bt_scale.data_ptr() if bt_scale is not None else None
-    _check(lib().amdprobe_gemm_f8_check(a.data_ptr(), bt.data_ptr(), c.data_ptr(), m, n, k, fa, fb, sa, sb, inject,
-                                        out.data_ptr(), _stream(a.device)), "gemm_f8_check")
-    o = out.cpu()
-    return float(o[0]), float(o[1])
-
-
-def _f4_operands(what: str, a, bt, a_scale, bt_scale, granule: int, k_granule: int, k_max=None, extra=()):
-    """Validates packed FP4 operands (and block scales) before native code sees them; returns
-    ``(a, bt, a_scale, bt_scale, m, n, k)`` with contiguous uint8 tensors. ``extra``: further ``(name, tensor)``
-    pairs (the output) that must be on the operands' GPU."""
-    import torch
-
-    packed = (torch.uint8, getattr(torch, "float4_e2m1fn_x2", torch.uint8))
-    if a.dtype not in packed or bt.dtype not in packed:
-        raise ProbeError(f"{what} expects packed E2M1 operands (uint8 or float4_e2m1fn_x2), got {a.dtype} and "
-                         f"{bt.dtype}")
-    if a.dim() != 2 or bt.dim() != 2 or a.shape[1] != bt.shape[1]:
-        raise ProbeError(f"{what} shape mismatch: {tuple(a.shape)} x {tuple(bt.shape)}^T (packed, K/2 bytes per row)")
-    m, k = a.shape[0], 2 * a.shape[1]
-    n = bt.shape[0]
-    if m % granule or n % granule or k % k_granule or m == 0 or n == 0 or k == 0 or (k_max and k > k_max):
-        raise ProbeError(f"{what} needs M,N % {granule} == 0 and K % {k_granule} == 0"
-                         f"{f' and K <= {k_max}' if k_max else ''}, got {m}x{n}x{k}")
-    if (a_scale is None) != (bt_scale is None):
-        raise ProbeError(f"{what}: block scales come in pairs (a_scale and bt_scale, or neither)")
-    if a_scale is not None:
-        for name, sc, rows in (("a_scale", a_scale, m), ("bt_scale", bt_scale, n)):
-            if sc.dtype != torch.uint8 or tuple(sc.shape) != (rows, k // F8_BLOCK):
-                raise ProbeError(f"{what}: {name} must be uint8 [{rows}, {k // F8_BLOCK}], got {sc.dtype} "
-                                 f"{tuple(sc.shape)}")
-        a_scale, bt_scale = a_scale.contiguous(), bt_scale.contiguous()
-    # last, so that a wrong shape is reported as such: every tensor on one GPU (the kernel gets raw pointers)
-    for name, t in (("a", a), ("bt", bt), ("a_scale", a_scale), ("bt_scale", bt_scale)) + tuple(extra):
-        if t is not None and (t.device.type != "cuda" or t.device != a.device):
-            raise ProbeError(f"{what}: {name} is on {t.device}; all operands must be on one GPU (a is on {a.device})")
-    return a.contiguous().view(torch.uint8), bt.contiguous().view(torch.uint8), a_scale, bt_scale, m, n, k
+    a, bt, a_scale, bt_scale, c, m, n, k, fmt = _operands("gemm_f8_check", "fp8", a, bt, _CHECK_TILE, F8_BLOCK,
+                                                          _CHECK_MAX_K, a_scale, bt_scale, c=c)
+    return _run_check("gemm_f8_check", lib().amdprobe_gemm_f8_check, a.device, a.data_ptr(), bt.data_ptr(),
+                      c.data_ptr(), m, n, k, *fmt, *_scale_ptrs(a_scale, bt_scale), inject)
 
 
 def gemm_f4_nt(a, bt, a_scale=None, bt_scale=None, out=None):
@@ -322,18 +297,10 @@ def gemm_f4_nt(a, bt, a_scale=None, bt_scale=None, out=None):
     ``cbsz:4 blgp:4``); M, N % 256 == 0, K % 256 == 0. ``a`` / ``bt`` are packed OCP E2M1, ``[rows, K/2]``
     ``uint8`` or ``float4_e2m1fn_x2`` (element ``2j`` in bits 3:0 of byte ``j``). With ``a_scale[M, K/32]`` and
     ``bt_scale[N, K/32]`` (uint8 E8M0) the product is MXFP4, block-scaled by the instruction's scale inputs."""
-    import torch
-
-    a, bt, a_scale, bt_scale, m, n, k = _f4_operands("gemm_f4_nt", a, bt, a_scale, bt_scale, F4_TILE_MN, F4_TILE_K,
-                                                     extra=(("out", out),))
-    if out is None:
-        out = torch.empty((m, n), dtype=torch.float32, device=a.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (m, n) or not out.is_contiguous():
-        raise ProbeError(f"gemm_f4_nt: out must be a contiguous float32 {(m, n)}, got {out.dtype} {tuple(out.shape)}")
-    sa = a_scale.data_ptr() if a_scale is not None else None
-    sb = bt_scale.data_ptr() if bt_scale is not None else None
-    _check(lib().amdprobe_gemm_f4_nt(a.data_ptr(), bt.data_ptr(), out.data_ptr(), m, n, k, sa, sb,
-                                     _stream(a.device)), "gemm_f4_nt")
+    a, bt, a_scale, bt_scale, out, m, n, k, _ = _operands("gemm_f4_nt", "fp4", a, bt, F4_TILE_MN, F4_TILE_K,
+                                                          a_scale=a_scale, bt_scale=bt_scale, out=out)
+    _check(lib().amdprobe_gemm_f4_nt(a.data_ptr(), bt.data_ptr(), out.data_ptr(), m, n, k,
+                                     *_scale_ptrs(a_scale, bt_scale), _stream(a.device)), "gemm_f4_nt")
     return out
 
 
@@ -341,20 +308,10 @@ def gemm_f4_check(a, bt, c, a_scale=None, bt_scale=None, inject: int = 0):
     """Dense check of an FP4 (or MXFP4) product ``c`` on the GPU, every element against an fp32 VALU
     reference decoded with integer arithmetic: returns ``(sum((c - ref)^2), sum(ref^2))``.
     M, N % 16 == 0, K % 32 == 0, K <= 1024."""
-    import torch
-
-    a, bt, a_scale, bt_scale, m, n, k = _f4_operands("gemm_f4_check", a, bt, a_scale, bt_scale, 16, F8_BLOCK, 1024,
-                                                     extra=(("c", c),))
-    if c.dtype != torch.float32 or tuple(c.shape) != (m, n):
-        raise ProbeError(f"gemm_f4_check: c must be float32 {(m, n)}, got {c.dtype} {tuple(c.shape)}")
-    c = c.contiguous()
-    out = torch.zeros(4, dtype=torch.float32, device=a.device)
-    sa = a_scale.data_ptr() if a_scale is not None else None
-    sb = bt_scale.data_ptr() if bt_scale is not None else None
-    _check(lib().amdprobe_gemm_f4_check(a.data_ptr(), bt.data_ptr(), c.data_ptr(), m, n, k, sa, sb, inject,
-                                        out.data_ptr(), _stream(a.device)), "gemm_f4_check")
-    o = out.cpu()
-    return float(o[0]), float(o[1])
+    a, bt, a_scale, bt_scale, c, m, n, k, _ = _operands("gemm_f4_check", "fp4", a, bt, _CHECK_TILE, F8_BLOCK,
+                                                        _CHECK_MAX_K, a_scale, bt_scale, c=c)
+    return _run_check("gemm_f4_check", lib().amdprobe_gemm_f4_check, a.device, a.data_ptr(), bt.data_ptr(),
+                      c.data_ptr(), m, n, k, *_scale_ptrs(a_scale, bt_scale), inject)
 
 
 def f8_fill(buf, seed: int, kind: str = "e4m3"):

@@ -1,6 +1,6 @@
 // FP4 / MXFP4 MFMA kernels of the readiness probe (gfx950). #included after f8_kernels.hip (uses its
-// intx4 / intx8, glds4, f8_fill_kernel and probe_kernels.hip's floatx4, xcd_remap, grouped_tile,
-// glds16, CHECK_TILE).
+// intx4 / intx8, glds4 and probe_kernels.hip's floatx4, xcd_remap, grouped_tile, glds16 and the
+// shared parts of the dense check).
 //
 // FP4 (OCP E2M1, with E8M0 block scales "MXFP4") goes through a part of the f8f6f4 operand path that
 // the FP8 kernels never reach: format select cbsz:4 blgp:4, 16 bytes (four VGPRs, 32 packed nibbles)
@@ -336,17 +336,14 @@ void gemm_f4_nt_kernel(const uint8_t* __restrict__ A, const uint8_t* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------
-// Dense check of the FP4 product, the counterpart of gemm_f8_check_kernel: one workgroup per 16x16
-// output tile, the tile's 16 A rows and 16 Bt rows (K/2 bytes each) staged in LDS, rows padded by
-// 16 B. The reference never touches the matrix pipe and uses no FP4 conversion hardware either:
-// every nibble is decoded with integer bit arithmetic on the VALU (E2M1 magnitude codes 0..7 =
-// 0, .5, 1, 1.5, 2, 3, 4, 6; bit 3 = sign), products are summed with fp32 FMAs 32 elements (16
-// bytes) at a time, and with scales each block's partial sum is multiplied by 2^(sa + sb - 254)
-// with ldexpf. Ends in two float atomics per workgroup into out2 (diff^2, ref^2; the caller zeroes
-// them). Needs M, N % 16 == 0, K % 32 == 0, K <= F4_CHECK_MAX_K (host-checked). `inject` = 1 reads
-// C[0:16][0:16] as zeros.
+// Dense check of the FP4 product, the counterpart of gemm_f8_check_kernel on the same staging and
+// finish (probe_kernels.hip), rows of K/2 bytes. The reference never touches the matrix pipe and
+// uses no FP4 conversion hardware either: every nibble is decoded with integer bit arithmetic on
+// the VALU (E2M1 magnitude codes 0..7 = 0, .5, 1, 1.5, 2, 3, 4, 6; bit 3 = sign), products are
+// summed with fp32 FMAs 32 elements (16 bytes) at a time, and with scales each block's partial sum
+// is multiplied by 2^(sa + sb - 254) with ldexpf. Needs M, N % 16 == 0, K % 32 == 0,
+// K <= CHECK_MAX_K (host-checked).
 // ---------------------------------------------------------------------------------------
-constexpr int F4_CHECK_MAX_K = 1024;
 
 __device__ __forceinline__ float e2m1_decode(uint32_t code) {
   const uint32_t mag = code & 7u;
@@ -359,31 +356,18 @@ __global__ __launch_bounds__(CHECK_THREADS)
 void gemm_f4_check_kernel(const uint8_t* __restrict__ A, const uint8_t* __restrict__ Bt, const float* __restrict__ C,
                           const uint8_t* __restrict__ sa, const uint8_t* __restrict__ sb, int M, int N, int K,
                           int inject, float* __restrict__ out2) {
-  __shared__ __attribute__((aligned(16))) uint8_t la[CHECK_TILE * (F4_CHECK_MAX_K / 2 + 16)];
-  __shared__ __attribute__((aligned(16))) uint8_t lb[CHECK_TILE * (F4_CHECK_MAX_K / 2 + 16)];
-  __shared__ uint8_t lsa[CHECK_TILE * (F4_CHECK_MAX_K / 32)], lsb[CHECK_TILE * (F4_CHECK_MAX_K / 32)];
-  __shared__ float red[2][CHECK_THREADS / 64];
-  const int tiles_n = N / CHECK_TILE;
-  const int tm = blockIdx.x / tiles_n, tn = blockIdx.x - tm * tiles_n;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ __attribute__((aligned(16))) uint8_t la[CHECK_TILE * (CHECK_MAX_K / 2 + 16)];
+  __shared__ __attribute__((aligned(16))) uint8_t lb[CHECK_TILE * (CHECK_MAX_K / 2 + 16)];
+  __shared__ uint8_t lsa[CHECK_TILE * (CHECK_MAX_K / 32)], lsb[CHECK_TILE * (CHECK_MAX_K / 32)];
+  const CheckPos t(N);
+  const int r = t.r, c = t.c;
   const int kblocks = K / 32;                  // 32 elements = one 16-B chunk = one scale block
-  const int kbytes = K / 2, row = kbytes + 16; // global / LDS row stride (bytes)
   const bool scaled = sa != nullptr;
-  for (int i = tid; i < CHECK_TILE * kblocks; i += CHECK_THREADS) {
-    const int r = i / kblocks, kb = i - r * kblocks;
-    *reinterpret_cast<uint4*>(la + r * row + kb * 16) =
-        *reinterpret_cast<const uint4*>(A + (size_t)(tm * CHECK_TILE + r) * kbytes + kb * 16);
-    *reinterpret_cast<uint4*>(lb + r * row + kb * 16) =
-        *reinterpret_cast<const uint4*>(Bt + (size_t)(tn * CHECK_TILE + r) * kbytes + kb * 16);
-    if (scaled) {
-      lsa[i] = sa[(size_t)(tm * CHECK_TILE + r) * kblocks + kb];
-      lsb[i] = sb[(size_t)(tn * CHECK_TILE + r) * kblocks + kb];
-    }
-  }
+  check_stage_rows(A, Bt, t, K / 2, la, lb);
+  if (scaled) check_stage_scales(sa, sb, t, kblocks, lsa, lsb);
   __syncthreads();
-  const int r = tid >> 4, c = tid & 15;
-  const uint8_t* pa = la + r * row;
-  const uint8_t* pb = lb + c * row;
+  const uint8_t* pa = la + r * (K / 2 + 16);
+  const uint8_t* pb = lb + c * (K / 2 + 16);
   float ref = 0.f;
   for (int kb = 0; kb < kblocks; ++kb) {
     const uint4 a4 = *reinterpret_cast<const uint4*>(pa + kb * 16);
@@ -401,35 +385,7 @@ void gemm_f4_check_kernel(const uint8_t* __restrict__ A, const uint8_t* __restri
     if (scaled) p = ldexpf(p, (int)lsa[r * kblocks + kb] + (int)lsb[c * kblocks + kb] - 254);
     ref += p;
   }
-  const int m = tm * CHECK_TILE + r, n = tn * CHECK_TILE + c;
-  float cv = C[(size_t)m * N + n];
-  if (inject == 1 && m < 16 && n < 16) cv = 0.f;   // a lost 16x16 tile
-  const float d = cv - ref;
-  float d2 = d * d, w2 = ref * ref;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    d2 += __shfl_xor(d2, off, 64);
-    w2 += __shfl_xor(w2, off, 64);
-  }
-  if (lane == 0) {
-    red[0][wave] = d2;
-    red[1][wave] = w2;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    float a = 0.f, b = 0.f;
-#pragma unroll
-    for (int w = 0; w < CHECK_THREADS / 64; ++w) {
-      a += red[0][w];
-      b += red[1][w];
-    }
-    atomicAdd(&out2[0], a);
-    atomicAdd(&out2[1], b);
-  }
+  check_finish(C, N, t, ref, inject, out2);
 }
-
-// Fill: every byte value is two finite E2M1 codes, so FP4 operands are plain hashed bytes:
-// f8_fill_kernel with mask 0xFFFFFFFF, add 0. Block scales reuse F8_FILL_SCALE.
-enum { F4_FILL_E2M1 = 3 };
 
 }  // namespace amdprobe

@@ -1,5 +1,5 @@
 // FP8 / MXFP8 MFMA kernels of the readiness probe (gfx950). #included after probe_kernels.hip
-// (uses its floatx4, xcd_remap, grouped_tile, glds16, mix32).
+// (uses its floatx4, xcd_remap, grouped_tile, glds16 and the shared parts of the dense check).
 //
 // The bf16 kernels exercise v_mfma_f32_16x16x32_bf16 only. FP8 and block-scaled (MX) payloads run
 // on a different part of the matrix pipe: the f8f6f4 instructions with a 32-byte-per-lane operand
@@ -217,18 +217,12 @@ void gemm_f8_nt_kernel(const uint8_t* __restrict__ A, const uint8_t* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------
-// Dense check of the FP8 product, the counterpart of gemm_check_kernel: one workgroup per 16x16
-// output tile, the tile's 16 A rows and 16 Bt rows staged in LDS (rows padded by 16 B: the row
-// stride in 16-B chunks, K / 16 + 1, is odd for K % 32 == 0, so the 16 Bt rows a lane group reads
-// at one k sit in 16 distinct slots of the bank window; the A row is a broadcast). Every
-// element's reference never touches the matrix pipe: bytes are decoded on the VALU
-// (v_cvt_pk_f32_fp8 / _bf8) and summed with fp32 FMAs, 32 elements at a time; with scales each
-// 32-element partial sum is multiplied by 2^(sa - 127) * 2^(sb - 127) with ldexpf. Ends in two
-// float atomics per workgroup into out2 (diff^2, ref^2; the caller zeroes them). Needs
-// M, N % 16 == 0, K % 32 == 0, K <= F8_CHECK_MAX_K (host-checked). `inject` = 1 reads
-// C[0:16][0:16] as zeros.
+// Dense check of the FP8 product, the counterpart of gemm_check_kernel on its staging and finish
+// (probe_kernels.hip). Every element's reference never touches the matrix pipe: bytes are decoded
+// on the VALU (v_cvt_pk_f32_fp8 / _bf8) and summed with fp32 FMAs, 32 elements at a time; with
+// scales each 32-element partial sum is multiplied by 2^(sa - 127) * 2^(sb - 127) with ldexpf.
+// Needs M, N % 16 == 0, K % 32 == 0, K <= CHECK_MAX_K (host-checked).
 // ---------------------------------------------------------------------------------------
-constexpr int F8_CHECK_MAX_K = 1024;
 
 template <int F>
 __device__ __forceinline__ void f8_decode4(uint32_t w, float* o) {
@@ -248,33 +242,17 @@ __global__ __launch_bounds__(CHECK_THREADS)
 void gemm_f8_check_kernel(const uint8_t* __restrict__ A, const uint8_t* __restrict__ Bt, const float* __restrict__ C,
                           const uint8_t* __restrict__ sa, const uint8_t* __restrict__ sb, int M, int N, int K,
                           int inject, float* __restrict__ out2) {
-  __shared__ __attribute__((aligned(16))) uint8_t la[CHECK_TILE * (F8_CHECK_MAX_K + 16)];
-  __shared__ __attribute__((aligned(16))) uint8_t lb[CHECK_TILE * (F8_CHECK_MAX_K + 16)];
-  __shared__ uint8_t lsa[CHECK_TILE * (F8_CHECK_MAX_K / 32)], lsb[CHECK_TILE * (F8_CHECK_MAX_K / 32)];
-  __shared__ float red[2][CHECK_THREADS / 64];
-  const int tiles_n = N / CHECK_TILE;
-  const int tm = blockIdx.x / tiles_n, tn = blockIdx.x - tm * tiles_n;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int row = K + 16;                      // LDS row stride (bytes)
-  const int kchunks = K / 16, kblocks = K / 32;
+  __shared__ __attribute__((aligned(16))) uint8_t la[CHECK_TILE * (CHECK_MAX_K + 16)];
+  __shared__ __attribute__((aligned(16))) uint8_t lb[CHECK_TILE * (CHECK_MAX_K + 16)];
+  __shared__ uint8_t lsa[CHECK_TILE * (CHECK_MAX_K / 32)], lsb[CHECK_TILE * (CHECK_MAX_K / 32)];
+  const CheckPos t(N);
+  const int r = t.r, c = t.c, kblocks = K / 32;
   const bool scaled = sa != nullptr;
-  for (int i = tid; i < CHECK_TILE * kchunks; i += CHECK_THREADS) {
-    const int r = i / kchunks, kc = i - r * kchunks;
-    *reinterpret_cast<uint4*>(la + r * row + kc * 16) =
-        *reinterpret_cast<const uint4*>(A + (size_t)(tm * CHECK_TILE + r) * K + kc * 16);
-    *reinterpret_cast<uint4*>(lb + r * row + kc * 16) =
-        *reinterpret_cast<const uint4*>(Bt + (size_t)(tn * CHECK_TILE + r) * K + kc * 16);
-  }
-  if (scaled)
-    for (int i = tid; i < CHECK_TILE * kblocks; i += CHECK_THREADS) {
-      const int r = i / kblocks, kb = i - r * kblocks;
-      lsa[i] = sa[(size_t)(tm * CHECK_TILE + r) * kblocks + kb];
-      lsb[i] = sb[(size_t)(tn * CHECK_TILE + r) * kblocks + kb];
-    }
+  check_stage_rows(A, Bt, t, K, la, lb);
+  if (scaled) check_stage_scales(sa, sb, t, kblocks, lsa, lsb);
   __syncthreads();
-  const int r = tid >> 4, c = tid & 15;
-  const uint8_t* pa = la + r * row;
-  const uint8_t* pb = lb + c * row;
+  const uint8_t* pa = la + r * (K + 16);
+  const uint8_t* pb = lb + c * (K + 16);
   float ref = 0.f;
   for (int kb = 0; kb < kblocks; ++kb) {
     float p0 = 0.f, p1 = 0.f;
@@ -298,56 +276,7 @@ void gemm_f8_check_kernel(const uint8_t* __restrict__ A, const uint8_t* __restri
     if (scaled) p = ldexpf(p, (int)lsa[r * kblocks + kb] + (int)lsb[c * kblocks + kb] - 254);
     ref += p;
   }
-  const int m = tm * CHECK_TILE + r, n = tn * CHECK_TILE + c;
-  float cv = C[(size_t)m * N + n];
-  if (inject == 1 && m < 16 && n < 16) cv = 0.f;   // a lost 16x16 tile
-  const float d = cv - ref;
-  float d2 = d * d, w2 = ref * ref;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    d2 += __shfl_xor(d2, off, 64);
-    w2 += __shfl_xor(w2, off, 64);
-  }
-  if (lane == 0) {
-    red[0][wave] = d2;
-    red[1][wave] = w2;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    float a = 0.f, b = 0.f;
-#pragma unroll
-    for (int w = 0; w < CHECK_THREADS / 64; ++w) {
-      a += red[0][w];
-      b += red[1][w];
-    }
-    atomicAdd(&out2[0], a);
-    atomicAdd(&out2[1], b);
-  }
-}
-
-// Hashed bytes for the readiness operands: every byte is (hash & and_mask) + add, replicated over
-// the dword. Always finite, random sign and mantissa, |x| in [0.5, 1):
-//   E4M3  and 0x87, add 0x30 (exponent 6 of bias 7; 0x7F / 0xFF, the NaNs, cannot occur)
-//   E5M2  and 0x83, add 0x38 (exponent 14 of bias 15; exponent 31, inf / NaN, cannot occur)
-//   E8M0 block scales  and 0x07, add 124: eight values 2^-3 .. 2^4 around 127, so a scale taken
-//   from the wrong row, block or byte lane changes the product.
-// The masks never carry between bytes. `zero2`, when given, is cleared (the check's diff2 / ref2).
-enum { F8_FILL_E4M3 = 0, F8_FILL_E5M2 = 1, F8_FILL_SCALE = 2 };
-
-__global__ __launch_bounds__(256)
-void f8_fill_kernel(uint4* __restrict__ p, size_t n16, uint32_t seed, uint32_t and4, uint32_t add4,
-                    float* __restrict__ zero2) {
-  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = tid; i < n16; i += stride) {
-    const uint64_t base = (i << 2) ^ ((uint64_t)seed << 40);
-    p[i] = make_uint4((mix32(base) & and4) + add4, (mix32(base + 1) & and4) + add4,
-                      (mix32(base + 2) & and4) + add4, (mix32(base + 3) & and4) + add4);
-  }
-  if (tid == 0 && zero2 != nullptr) {
-    zero2[0] = 0.f;
-    zero2[1] = 0.f;
-  }
+  check_finish(C, N, t, ref, inject, out2);
 }
 
 }  // namespace amdprobe

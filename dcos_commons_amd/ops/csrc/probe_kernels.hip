@@ -423,21 +423,6 @@ void pattern_write_kernel(uint4* __restrict__ p, size_t n16, uint32_t seed) {
   }
 }
 
-// Finite bf16 operands with random sign/mantissa bits and |x| in [0.5, 1) (benchmark fill).
-__global__ __launch_bounds__(256)
-void bf16_fill_kernel(uint4* __restrict__ p, size_t n16, uint32_t seed) {
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride) {
-    const uint64_t base = (i << 2) ^ ((uint64_t)seed << 40);
-    uint4 v = make_uint4(mix32(base), mix32(base + 1), mix32(base + 2), mix32(base + 3));
-    v.x = (v.x & 0x807F807Fu) | 0x3F003F00u;
-    v.y = (v.y & 0x807F807Fu) | 0x3F003F00u;
-    v.z = (v.z & 0x807F807Fu) | 0x3F003F00u;
-    v.w = (v.w & 0x807F807Fu) | 0x3F003F00u;
-    p[i] = v;
-  }
-}
-
 __global__ __launch_bounds__(256)
 void pattern_check_kernel(const uint4* __restrict__ p, size_t n16, uint32_t seed,
                           unsigned long long* __restrict__ errors) {
@@ -458,7 +443,7 @@ void pattern_check_kernel(const uint4* __restrict__ p, size_t n16, uint32_t seed
 // Fused readiness check. A pod's readiness probe is on the deploy / recovery critical path, so
 // it runs as ONE host call: five launches back to back on a private stream and a single 32-byte
 // read-back, instead of a chain of framework ops with a host sync in the middle.
-//   readiness_prep_kernel  A, Bt <- hashed bf16 operands, result <- 0
+//   hashed_fill_kernel     A, Bt <- hashed bf16 operands, result <- 0
 //   gemm (MFMA)            C = A Bt^T
 //   gemm_check_kernel      every element of C against an fp32 VALU reference (v_dot2_f32_bf16)
 //   pattern_write/check    address-hashed write + verify over a 64 MiB buffer
@@ -470,74 +455,89 @@ struct ReadinessResult {
   unsigned long long reserved;
 };
 
+// Hashed operand fill: every dword is (hash & and4) + add4, the per-byte (or per-bf16) mask pair
+// replicated over the dword; the masks never carry between elements. All kinds but E2M1 are
+// finite with a random sign and mantissa and |x| in [0.5, 1):
+//   E4M3  and 0x87, add 0x30 (exponent 6 of bias 7; 0x7F / 0xFF, the NaNs, cannot occur)
+//   E5M2  and 0x83, add 0x38 (exponent 14 of bias 15; exponent 31, inf / NaN, cannot occur)
+//   E8M0 block scales  and 0x07, add 124: eight values 2^-3 .. 2^4 around 127, so a scale taken
+//         from the wrong row, block or byte lane changes the product
+//   E2M1  any byte: every byte value is two finite FP4 codes
+//   bf16  and 0x807F, add 0x3F00 (exponent 126 of bias 127)
+// The first four values are the `kind` of amdprobe_f8_fill. `res`, when given, is zeroed: the
+// result slot of the checks that follow on the stream.
+enum { FILL_E4M3 = 0, FILL_E5M2 = 1, FILL_SCALE = 2, FILL_E2M1 = 3, FILL_BF16 = 4, FILL_KINDS = 5 };
+constexpr uint32_t FILL_AND4[FILL_KINDS] = {0x87878787u, 0x83838383u, 0x07070707u, 0xFFFFFFFFu, 0x807F807Fu};
+constexpr uint32_t FILL_ADD4[FILL_KINDS] = {0x30303030u, 0x38383838u, 0x7C7C7C7Cu, 0u, 0x3F003F00u};
+
 __global__ __launch_bounds__(256)
-void readiness_prep_kernel(uint4* __restrict__ ab, size_t ab16, uint32_t seed, ReadinessResult* __restrict__ res) {
+void hashed_fill_kernel(uint4* __restrict__ p, size_t n16, uint32_t seed, uint32_t and4, uint32_t add4,
+                        ReadinessResult* __restrict__ res) {
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = tid; i < ab16; i += stride) {
+  for (size_t i = tid; i < n16; i += stride) {
     const uint64_t base = (i << 2) ^ ((uint64_t)seed << 40);
-    uint4 v = make_uint4(mix32(base), mix32(base + 1), mix32(base + 2), mix32(base + 3));
-    // finite bf16 pairs: random sign and mantissa, |x| in [0.5, 1)
-    v.x = (v.x & 0x807F807Fu) | 0x3F003F00u;
-    v.y = (v.y & 0x807F807Fu) | 0x3F003F00u;
-    v.z = (v.z & 0x807F807Fu) | 0x3F003F00u;
-    v.w = (v.w & 0x807F807Fu) | 0x3F003F00u;
-    ab[i] = v;
+    p[i] = make_uint4((mix32(base) & and4) + add4, (mix32(base + 1) & and4) + add4,
+                      (mix32(base + 2) & and4) + add4, (mix32(base + 3) & and4) + add4);
   }
-  if (tid == 0) {
-    res->diff2 = 0.f;
-    res->ref2 = 0.f;
-    res->bad_words = 0ull;
-    res->reserved = 0ull;
-  }
+  if (tid == 0 && res != nullptr) *res = ReadinessResult{0.f, 0.f, 0ull, 0ull};
 }
 
-// Dense check of C = A Bt^T: one workgroup per 16 x 16 output tile (M / 16 * N / 16 of them, so
-// a 256 x 256 product spreads over 256 CUs). The tile's 16 A rows and 16 Bt rows are staged in
-// LDS (rows padded by 16 B: the 16 Bt rows a wave reads at one k land on disjoint bank groups),
-// each thread forms its element's fp32 reference with v_dot2_f32_bf16 (two accumulators), and
-// the workgroup adds its sum of squared differences and of squared references to out2 with two
-// float atomics (out2 must arrive zeroed; the prep kernel zeroes it). Needs M, N % 16 == 0,
-// K % 8 == 0, K <= CHECK_MAX_K (host-checked). `inject` = 1 reads C[0:16][0:16] as zeros, a
-// lost MFMA tile (tests that the check catches it).
+// Dense check of C = A Bt^T, shared by the bf16, FP8 and FP4 check kernels: one workgroup per
+// 16 x 16 output tile (M / 16 * N / 16 of them, so a 256 x 256 product spreads over 256 CUs).
+// The tile's 16 A rows and 16 Bt rows are staged in LDS as bytes, each thread forms the fp32
+// reference of its element on the VALU (the part that differs per format), and the workgroup
+// adds its sum of squared differences and of squared references to out2 with two float atomics
+// (out2 must arrive zeroed; the fill kernel zeroes it). Needs M, N % 16 == 0, a row of a multiple
+// of 16 bytes and K <= CHECK_MAX_K (host-checked).
 constexpr int CHECK_TILE = 16;
 constexpr int CHECK_THREADS = CHECK_TILE * CHECK_TILE;
 constexpr int CHECK_MAX_K = 1024;
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
-__global__ __launch_bounds__(CHECK_THREADS)
-void gemm_check_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bt, const float* __restrict__ C,
-                       int M, int N, int K, int inject, float* __restrict__ out2) {
-  __shared__ __attribute__((aligned(16))) __bf16 la[CHECK_TILE * (CHECK_MAX_K + 8)];
-  __shared__ __attribute__((aligned(16))) __bf16 lb[CHECK_TILE * (CHECK_MAX_K + 8)];
+// This workgroup's tile and this thread's element of it.
+struct CheckPos {
+  int tm, tn, r, c;
+  __device__ CheckPos(int N) {
+    const int tiles_n = N / CHECK_TILE;
+    tm = blockIdx.x / tiles_n, tn = blockIdx.x - tm * tiles_n;
+    r = threadIdx.x >> 4, c = threadIdx.x & 15;
+  }
+};
+
+// Rows of `row_bytes` in global memory go to LDS rows of row_bytes + 16: with the pad, the 16 Bt
+// rows a lane group reads at one k sit in 16 distinct 16-B slots of the bank window (the row
+// stride in 16-B chunks is odd for row_bytes % 32 == 0); the A row is a broadcast.
+__device__ __forceinline__ void check_stage_rows(const void* __restrict__ A, const void* __restrict__ Bt,
+                                                 const CheckPos& t, int row_bytes, uint8_t* la, uint8_t* lb) {
+  const uint8_t *a = static_cast<const uint8_t*>(A), *b = static_cast<const uint8_t*>(Bt);
+  const int row = row_bytes + 16, chunks = row_bytes / 16;
+  for (int i = threadIdx.x; i < CHECK_TILE * chunks; i += CHECK_THREADS) {
+    const int r = i / chunks, kc = i - r * chunks;
+    *reinterpret_cast<uint4*>(la + r * row + kc * 16) =
+        *reinterpret_cast<const uint4*>(a + (size_t)(t.tm * CHECK_TILE + r) * row_bytes + kc * 16);
+    *reinterpret_cast<uint4*>(lb + r * row + kc * 16) =
+        *reinterpret_cast<const uint4*>(b + (size_t)(t.tn * CHECK_TILE + r) * row_bytes + kc * 16);
+  }
+}
+
+// The tile's E8M0 block scales, [16][kblocks] bytes per operand (FP8 / FP4 with scales).
+__device__ __forceinline__ void check_stage_scales(const uint8_t* __restrict__ sa, const uint8_t* __restrict__ sb,
+                                                   const CheckPos& t, int kblocks, uint8_t* lsa, uint8_t* lsb) {
+  for (int i = threadIdx.x; i < CHECK_TILE * kblocks; i += CHECK_THREADS) {
+    const int r = i / kblocks, kb = i - r * kblocks;
+    lsa[i] = sa[(size_t)(t.tm * CHECK_TILE + r) * kblocks + kb];
+    lsb[i] = sb[(size_t)(t.tn * CHECK_TILE + r) * kblocks + kb];
+  }
+}
+
+// Compares this thread's element of C with `ref` and adds the workgroup's two sums to out2.
+// `inject` = 1 reads C[0:16][0:16] as zeros, a lost MFMA tile (tests that the check catches it).
+__device__ __forceinline__ void check_finish(const float* __restrict__ C, int N, const CheckPos& t, float ref,
+                                             int inject, float* __restrict__ out2) {
   __shared__ float red[2][CHECK_THREADS / 64];
-  const int tiles_n = N / CHECK_TILE;
-  const int tm = blockIdx.x / tiles_n, tn = blockIdx.x - tm * tiles_n;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int row = K + 8;                       // LDS row stride (bf16)
-  const int kchunks = K / 8;
-  for (int i = tid; i < CHECK_TILE * kchunks; i += CHECK_THREADS) {
-    const int r = i / kchunks, kc = i - r * kchunks;
-    *reinterpret_cast<uint4*>(la + r * row + kc * 8) =
-        *reinterpret_cast<const uint4*>(A + (size_t)(tm * CHECK_TILE + r) * K + kc * 8);
-    *reinterpret_cast<uint4*>(lb + r * row + kc * 8) =
-        *reinterpret_cast<const uint4*>(Bt + (size_t)(tn * CHECK_TILE + r) * K + kc * 8);
-  }
-  __syncthreads();
-  const int r = tid >> 4, c = tid & 15;
-  const __bf16* pa = la + r * row;
-  const __bf16* pb = lb + c * row;
-  float acc0 = 0.f, acc1 = 0.f;
-  for (int kc = 0; kc < kchunks; ++kc) {
-    const bf16x8 a8 = *reinterpret_cast<const bf16x8*>(pa + kc * 8);
-    const bf16x8 b8 = *reinterpret_cast<const bf16x8*>(pb + kc * 8);
-    acc0 = __builtin_amdgcn_fdot2_f32_bf16(bf16x2{a8[0], a8[1]}, bf16x2{b8[0], b8[1]}, acc0, false);
-    acc1 = __builtin_amdgcn_fdot2_f32_bf16(bf16x2{a8[2], a8[3]}, bf16x2{b8[2], b8[3]}, acc1, false);
-    acc0 = __builtin_amdgcn_fdot2_f32_bf16(bf16x2{a8[4], a8[5]}, bf16x2{b8[4], b8[5]}, acc0, false);
-    acc1 = __builtin_amdgcn_fdot2_f32_bf16(bf16x2{a8[6], a8[7]}, bf16x2{b8[6], b8[7]}, acc1, false);
-  }
-  const float ref = acc0 + acc1;
-  const int m = tm * CHECK_TILE + r, n = tn * CHECK_TILE + c;
+  const int m = t.tm * CHECK_TILE + t.r, n = t.tn * CHECK_TILE + t.c;
   float cv = C[(size_t)m * N + n];
   if (inject == 1 && m < 16 && n < 16) cv = 0.f;   // a lost 16x16 tile
   const float d = cv - ref;
@@ -562,6 +562,30 @@ void gemm_check_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ 
     atomicAdd(&out2[0], a);
     atomicAdd(&out2[1], b);
   }
+}
+
+// bf16: the reference is v_dot2_f32_bf16 into two accumulators. K % 8 == 0. Resources (hipcc -O3,
+// -Rpass-analysis=kernel-resource-usage, gfx950): 74 VGPRs, 66080 B LDS (2 workgroups per CU), no scratch.
+__global__ __launch_bounds__(CHECK_THREADS)
+void gemm_check_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bt, const float* __restrict__ C,
+                       int M, int N, int K, int inject, float* __restrict__ out2) {
+  __shared__ __attribute__((aligned(16))) uint8_t la[CHECK_TILE * (2 * CHECK_MAX_K + 16)];
+  __shared__ __attribute__((aligned(16))) uint8_t lb[CHECK_TILE * (2 * CHECK_MAX_K + 16)];
+  const CheckPos t(N);
+  check_stage_rows(A, Bt, t, 2 * K, la, lb);
+  __syncthreads();
+  const __bf16* pa = reinterpret_cast<const __bf16*>(la + t.r * (2 * K + 16));
+  const __bf16* pb = reinterpret_cast<const __bf16*>(lb + t.c * (2 * K + 16));
+  float acc0 = 0.f, acc1 = 0.f;
+  for (int kc = 0; kc < K / 8; ++kc) {
+    const bf16x8 a8 = *reinterpret_cast<const bf16x8*>(pa + kc * 8);
+    const bf16x8 b8 = *reinterpret_cast<const bf16x8*>(pb + kc * 8);
+    acc0 = __builtin_amdgcn_fdot2_f32_bf16(bf16x2{a8[0], a8[1]}, bf16x2{b8[0], b8[1]}, acc0, false);
+    acc1 = __builtin_amdgcn_fdot2_f32_bf16(bf16x2{a8[2], a8[3]}, bf16x2{b8[2], b8[3]}, acc1, false);
+    acc0 = __builtin_amdgcn_fdot2_f32_bf16(bf16x2{a8[4], a8[5]}, bf16x2{b8[4], b8[5]}, acc0, false);
+    acc1 = __builtin_amdgcn_fdot2_f32_bf16(bf16x2{a8[6], a8[7]}, bf16x2{b8[6], b8[7]}, acc1, false);
+  }
+  check_finish(C, N, t, acc0 + acc1, inject, out2);
 }
 
 }  // namespace amdprobe

@@ -166,10 +166,10 @@ void perf(hipStream_t st, Report& r) {
   HIP_OK(hipMalloc(&a, static_cast<size_t>(S) * S * 2));
   HIP_OK(hipMalloc(&b, static_cast<size_t>(S) * S * 2));
   HIP_OK(hipMalloc(&c, static_cast<size_t>(S) * S * 4));
-  hipLaunchKernelGGL(bf16_fill_kernel, dim3(2048), dim3(256), 0, st, static_cast<uint4*>(a),
-                     static_cast<size_t>(S) * S / 8, 11u);
-  hipLaunchKernelGGL(bf16_fill_kernel, dim3(2048), dim3(256), 0, st, static_cast<uint4*>(b),
-                     static_cast<size_t>(S) * S / 8, 12u);
+  for (void* p : {a, b})
+    hipLaunchKernelGGL(hashed_fill_kernel, dim3(2048), dim3(256), 0, st, static_cast<uint4*>(p),
+                       static_cast<size_t>(S) * S / 8, p == a ? 11u : 12u, FILL_AND4[FILL_BF16], FILL_ADD4[FILL_BF16],
+                       static_cast<ReadinessResult*>(nullptr));
   ms = time_ms(st, 5, [&] { launch_gemm(st, true, a, b, c, S, S, S); });
   r.gemm_tflops = 2.0 * S * S * static_cast<double>(S) / (ms / 1e3) / 1e12;
   HIP_OK(hipFree(a));

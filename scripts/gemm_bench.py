@@ -1,14 +1,16 @@
 """Interleaved A/B timing of the probe GEMM variants on uniform random [-1, 1) bf16 operands.
 
 Rounds alternate the variants in one process (cdna_hip_programming.md §5.4 rule 24); prints one
-JSON line per shape with the median and best TFLOP/s per variant and torch.matmul (hipBLASLt) as
-the library reference on the same data.
+JSON line per shape with the median, best and spread of TFLOP/s per variant and torch.matmul
+(hipBLASLt) as the library reference on the same data. The FP8 and FP4 bench scripts share the
+timing loop defined here.
 """
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 
 import torch
 
@@ -27,6 +29,36 @@ def time_ms(fn, reps):
     e1.record()
     e1.synchronize()
     return e0.elapsed_time(e1) / reps
+
+
+def host_ms(fn, reps=20):
+    """Median host time of a call, after one warm-up call."""
+    fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return round(statistics.median(ts), 4)
+
+
+def bench_arms(arms, flop, rounds, reps):
+    """Times the arms alternately over ``rounds``; returns ``(median TFLOP/s per arm, JSON fields)``: the
+    median, best and max - min spread of TFLOP/s per arm."""
+    res = {name: [] for name in arms}
+    for _ in range(rounds):
+        for name, fn in arms.items():
+            res[name].append(flop / (time_ms(fn, reps) * 1e-3) / 1e12)
+    med = {name: statistics.median(v) for name, v in res.items()}
+    return med, {**{f"{name}_tflops_median": round(v, 1) for name, v in med.items()},
+                 **{f"{name}_tflops_best": round(max(v), 1) for name, v in res.items()},
+                 **{f"{name}_tflops_spread": round(max(v) - min(v), 1) for name, v in res.items()}}
+
+
+def readiness_host_ms(modes):
+    """JSON fields: host time of a ``readiness`` call and of a ``readiness_f8`` call per mode."""
+    return {"readiness_bf16_host_ms": host_ms(lambda: ops.readiness(0, 1)),
+            **{f"readiness_{mode}_host_ms": host_ms(lambda: ops.readiness_f8(0, 1, mode)) for mode in modes}}
 
 
 def main():
@@ -49,17 +81,12 @@ def main():
             "tile128": lambda: ops.gemm_bf16_nt(a, bt, out, variant="tile128"),
             "torch_matmul_bf16out": lambda: torch.matmul(a, bt.t()),
         }
-        res = {name: [] for name in arms}
-        for _ in range(args.rounds):
-            for name, fn in arms.items():
-                res[name].append(flop / (time_ms(fn, args.reps) * 1e-3) / 1e12)
+        _, fields = bench_arms(arms, flop, args.rounds, args.reps)
         ref = a.float() @ bt.float().t()
         ops.gemm_bf16_nt(a, bt, out, variant="glds256")
         torch.cuda.synchronize()
         rel = (torch.linalg.norm(out - ref) / torch.linalg.norm(ref)).item()
-        print(json.dumps({"shape": [m, n, k], "rel_err_glds256": rel,
-                          **{f"{name}_tflops_median": round(statistics.median(v), 1) for name, v in res.items()},
-                          **{f"{name}_tflops_best": round(max(v), 1) for name, v in res.items()}}), flush=True)
+        print(json.dumps({"shape": [m, n, k], "rel_err_glds256": rel, **fields}), flush=True)
 
 
 if __name__ == "__main__":

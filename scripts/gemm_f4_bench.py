@@ -8,7 +8,6 @@ line with the host time of a ``readiness_f8`` call per mode next to ``readiness`
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -16,8 +15,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from dcos_commons_amd import ops
-from gemm_bench import time_ms
-from gemm_f8_bench import host_ms
+from gemm_bench import bench_arms, readiness_host_ms
 
 
 def main():
@@ -38,26 +36,16 @@ def main():
         sc = torch.empty((m + n, k // 32), dtype=torch.uint8, device=dev)
         ops.f8_fill(sc, seed=size + 1, kind="scale")
         out = torch.empty((m, n), device=dev, dtype=torch.float32)
-        flop = 2.0 * m * n * k
         arms = {
             "mxfp4": lambda: ops.gemm_f4_nt(a4, b4, sc[:m], sc[m:], out=out),
             "f4": lambda: ops.gemm_f4_nt(a4, b4, out=out),
             "mxfp8": lambda: ops.gemm_f8_nt(a8, b8, sc[:m], sc[m:], out=out),
             "f8_e4m3": lambda: ops.gemm_f8_nt(a8, b8, out=out),
         }
-        res = {name: [] for name in arms}
-        for _ in range(args.rounds):
-            for name, fn in arms.items():
-                res[name].append(flop / (time_ms(fn, args.reps) * 1e-3) / 1e12)
-        med = {name: statistics.median(v) for name, v in res.items()}
-        print(json.dumps({"shape": [m, n, k], "reps": args.reps, "rounds": args.rounds,
-                          **{f"{name}_tflops_median": round(v, 1) for name, v in med.items()},
-                          **{f"{name}_tflops_best": round(max(v), 1) for name, v in res.items()},
-                          **{f"{name}_tflops_spread": round(max(v) - min(v), 1) for name, v in res.items()},
+        med, fields = bench_arms(arms, 2.0 * m * n * k, args.rounds, args.reps)
+        print(json.dumps({"shape": [m, n, k], "reps": args.reps, "rounds": args.rounds, **fields,
                           "mxfp4_over_mxfp8": round(med["mxfp4"] / med["mxfp8"], 3)}), flush=True)
-    print(json.dumps({"readiness_bf16_host_ms": host_ms(lambda: ops.readiness(0, 1)),
-                      **{f"readiness_{mode}_host_ms": host_ms(lambda: ops.readiness_f8(0, 1, mode))
-                         for mode in ("fp8", "bf8", "mxfp8", "mxfp4")}}), flush=True)
+    print(json.dumps(readiness_host_ms(("fp8", "bf8", "mxfp8", "mxfp4"))), flush=True)
 
 
 if __name__ == "__main__":

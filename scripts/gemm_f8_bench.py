@@ -2,32 +2,20 @@
 
 Rounds alternate the arms in one process; every arm is timed with device events over ``--reps``
 launches after a warm-up launch. FLOPs are 2*M*N*K for every arm. Prints one JSON line per shape
-(median and best TFLOP/s per arm, and the f8 / tile128 ratio: same tile shape, half the bytes per
-K element) and one line with the host time of a ``readiness_f8`` call next to ``readiness``.
+(median, best and spread of TFLOP/s per arm, and the f8 / tile128 ratio: same tile shape, half the
+bytes per K element) and one line with the host time of a ``readiness_f8`` call next to ``readiness``.
 """
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from dcos_commons_amd import ops
-from gemm_bench import time_ms
-
-
-def host_ms(fn, reps=20):
-    fn()
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return round(statistics.median(ts), 4)
+from gemm_bench import bench_arms, readiness_host_ms
 
 
 def main():
@@ -49,26 +37,17 @@ def main():
         sc = torch.empty((m + n, k // 32), dtype=torch.uint8, device=dev)
         ops.f8_fill(sc, seed=size + 1, kind="scale")
         out = torch.empty((m, n), device=dev, dtype=torch.float32)
-        flop = 2.0 * m * n * k
         arms = {
             "f8_e4m3": lambda: ops.gemm_f8_nt(a8, b8, out=out),
             "mxfp8": lambda: ops.gemm_f8_nt(a8, b8, sc[:m], sc[m:], out=out),
             "bf16_tile128": lambda: ops.gemm_bf16_nt(a, bt, out, variant="tile128"),
             "bf16_glds256": lambda: ops.gemm_bf16_nt(a, bt, out, variant="glds256"),
         }
-        res = {name: [] for name in arms}
-        for _ in range(args.rounds):
-            for name, fn in arms.items():
-                res[name].append(flop / (time_ms(fn, args.reps) * 1e-3) / 1e12)
-        med = {name: statistics.median(v) for name, v in res.items()}
-        print(json.dumps({"shape": [m, n, k], "reps": args.reps, "rounds": args.rounds,
-                          **{f"{name}_tflops_median": round(v, 1) for name, v in med.items()},
-                          **{f"{name}_tflops_best": round(max(v), 1) for name, v in res.items()},
+        med, fields = bench_arms(arms, 2.0 * m * n * k, args.rounds, args.reps)
+        print(json.dumps({"shape": [m, n, k], "reps": args.reps, "rounds": args.rounds, **fields,
                           "f8_over_tile128": round(med["f8_e4m3"] / med["bf16_tile128"], 3),
                           "mxfp8_over_tile128": round(med["mxfp8"] / med["bf16_tile128"], 3)}), flush=True)
-    print(json.dumps({"readiness_bf16_host_ms": host_ms(lambda: ops.readiness(0, 1)),
-                      **{f"readiness_{mode}_host_ms": host_ms(lambda: ops.readiness_f8(0, 1, mode))
-                         for mode in ("fp8", "bf8", "mxfp8")}}), flush=True)
+    print(json.dumps(readiness_host_ms(("fp8", "bf8", "mxfp8"))), flush=True)
 
 
 if __name__ == "__main__":

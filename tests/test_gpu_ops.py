@@ -141,7 +141,7 @@ def test_readiness_probe_on_a_non_default_device(dev):
 
 
 # ---------------------------------------------------------------------------------------
-# fused readiness path (csrc/probe_kernels.hip readiness_prep_kernel / gemm_check_kernel,
+# fused readiness path (csrc/probe_kernels.hip hashed_fill_kernel / gemm_check_kernel,
 # csrc/probe_api.hip amdprobe_readiness)
 
 
@@ -198,6 +198,26 @@ def test_readiness_fill_matches_the_host_hash(dev):
     assert np.array_equal(ab.cpu().numpy().view(np.uint32), words)
     vals = ab.view(torch.bfloat16).float().abs()
     assert bool(((vals >= 0.5) & (vals < 1.0)).all())
+
+
+@pytest.mark.parametrize("kind,and1,add1", [("e4m3", 0x87, 0x30), ("e5m2", 0x83, 0x38), ("scale", 0x07, 0x7C),
+                                            ("e2m1", 0xFF, 0x00)])
+def test_f8_fill_kinds_match_the_host_hash(dev, kind, and1, add1):
+    """The one place where the fill's mask table is pinned byte for byte (bf16: the test above)."""
+    import numpy as np
+
+    from dcos_commons_amd import ops
+
+    seed = 4321
+    buf = torch.empty(16384, dtype=torch.uint8, device=dev)    # 1024 chunks of 16 B
+    ops.f8_fill(buf, seed, kind)
+    torch.cuda.synchronize()
+    with np.errstate(over="ignore"):
+        i = np.arange(1024, dtype=np.uint64)
+        base = (i << np.uint64(2)) ^ (np.uint64(seed) << np.uint64(40))
+        words = np.stack([_mix32(base + np.uint64(j)) for j in range(4)], axis=1).reshape(-1)
+    want = (words.view(np.uint8) & np.uint8(and1)) + np.uint8(add1)    # per byte: the masks never carry
+    assert np.array_equal(buf.cpu().numpy(), want)
 
 
 def test_fused_readiness_passes_and_catches_planted_faults(dev):
