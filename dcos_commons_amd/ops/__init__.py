@@ -1,11 +1,12 @@
 """MI355X device ops: HIP probe kernels behind a torch-tensor API.
 
-The kernels live in three files under ``csrc/``:
+The kernels live in four files under ``csrc/``:
 
 * ``probe_kernels.hip``: MFMA bf16 GEMM, MFMA issue-rate loop, HBM streaming copy, HBM pattern test,
   the hashed operand fill and the shared parts of the dense VALU check;
 * ``f8_kernels.hip``: FP8 / MXFP8 MFMA GEMM and its check;
-* ``f4_kernels.hip``: FP4 / MXFP4 MFMA GEMM and its check.
+* ``f4_kernels.hip``: FP4 / MXFP4 MFMA GEMM and its check;
+* ``i8_kernels.hip``: INT8 MFMA GEMM (int32 accumulators) and its exact check.
 
 They are compiled for gfx950 into the in-tree ``_amdprobe.so`` (``python -m dcos_commons_amd.ops.build``)
 and back the GPU readiness/health check that gates pods which request ``gpus``
@@ -60,6 +61,8 @@ def _bind(lib: ctypes.CDLL) -> None:
             ("f8_fill", i, [vp, sz, u, i, vp, vp]),
             ("gemm_f4_nt", i, [vp, vp, vp, i, i, i, vp, vp, vp]),
             ("gemm_f4_check", i, [vp, vp, vp, i, i, i, vp, vp, i, vp, vp]),
+            ("gemm_i8_nt", i, [vp, vp, vp, i, i, i, vp]),
+            ("gemm_i8_check", i, [vp, vp, vp, i, i, i, i, vp, vp]),
             ("readiness_f8", i, [i, u, i, i, pd])):
         fn = getattr(lib, "amdprobe_" + name)
         fn.restype = restype
@@ -97,10 +100,13 @@ def _check(rc: int, what: str) -> None:
 
 F8_TILE = 128                       # M, N and K granule of gemm_f8_nt
 F8_BLOCK = 32                       # K elements per E8M0 block scale
-F8_FILL_KINDS = {"e4m3": 0, "e5m2": 1, "scale": 2, "e2m1": 3}
-READINESS_F8_MODES = {"fp8": 0, "bf8": 1, "mxfp8": 2, "mxfp4": 3}
+F8_FILL_KINDS = {"e4m3": 0, "e5m2": 1, "scale": 2, "e2m1": 3, "i8": 3}   # i8: the any-byte fill
+READINESS_F8_MODES = {"fp8": 0, "bf8": 1, "mxfp8": 2, "mxfp4": 3, "int8": 4}
 F4_TILE_MN = 256                    # M and N granule of gemm_f4_nt
 F4_TILE_K = 256                     # K granule (elements) of gemm_f4_nt
+I8_TILE_MN = 256                    # M and N granule of gemm_i8_nt
+I8_TILE_K = 128                     # K granule of gemm_i8_nt
+I8_MAX_K = 65536                    # its largest K: no int32 sum of K products can wrap
 _CHECK_TILE = 16                    # M and N granule of the dense checks
 _CHECK_MAX_K = 1024                 # their largest K (one tile's operand rows sit in LDS)
 
@@ -109,8 +115,8 @@ def _operands(what: str, kind: str, a, bt, granule: int, k_granule: int, k_max=N
               out=None, c=None):
     """Validates the operands of a GEMM or check wrapper before native code sees their pointers; returns
     ``(a, bt, a_scale, bt_scale, res, m, n, k, fmt)`` with contiguous tensors. ``kind`` is ``bf16``, ``fp8``
-    (``fmt`` = the two format codes of the native call, else ``()``) or ``fp4`` (packed: K is twice the row
-    length; the operands come back as uint8). ``res`` is the product: ``c`` made contiguous when the caller
+    (``fmt`` = the two format codes of the native call, else ``()``), ``int8`` (the product is int32, not
+    float32) or ``fp4`` (packed: K is twice the row length; the operands come back as uint8). ``res`` is the product: ``c`` made contiguous when the caller
     has one to check, else ``out``, allocated when ``None``. Shape, granule, dtype and paired-scale errors
     are reported first; then every tensor must be on the operands' one GPU, and the product a float32
     ``(m, n)``, a caller's ``out`` contiguous as well (the kernel writes through its pointer)."""
@@ -126,6 +132,8 @@ def _operands(what: str, kind: str, a, bt, granule: int, k_granule: int, k_max=N
             fmt = (codes[a.dtype], codes[bt.dtype])
             if fmt == (1, 0):
                 raise ProbeError(f"{what}: E5M2 x E4M3 is not built (swap the operands: E4M3 x E5M2 is)")
+    elif kind == "int8":
+        ok, expects = a.dtype == bt.dtype == torch.int8, "int8"
     else:
         packed = (torch.uint8, getattr(torch, "float4_e2m1fn_x2", torch.uint8))
         ok, expects = a.dtype in packed and bt.dtype in packed, "packed E2M1 (uint8 or float4_e2m1fn_x2)"
@@ -150,15 +158,17 @@ def _operands(what: str, kind: str, a, bt, granule: int, k_granule: int, k_max=N
     for name, t in (("a", a), ("bt", bt), ("a_scale", a_scale), ("bt_scale", bt_scale), ("out", out), ("c", c)):
         if t is not None and (t.device.type != "cuda" or t.device != a.device):
             raise ProbeError(f"{what}: {name} is on {t.device}; all operands must be on one GPU (a is on {a.device})")
+    res_dtype = torch.int32 if kind == "int8" else torch.float32
     for name, t in (("out", out), ("c", c)):
-        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (m, n) or
+        if t is not None and (t.dtype != res_dtype or tuple(t.shape) != (m, n) or
                               (t is out and not t.is_contiguous())):
-            raise ProbeError(f"{what}: {name} must be a{' contiguous' if t is out else ''} float32 {(m, n)}, got "
+            raise ProbeError(f"{what}: {name} must be a{' contiguous' if t is out else ''} "
+                             f"{str(res_dtype).split('.')[-1]} {(m, n)}, got "
                              f"{t.dtype} {tuple(t.shape)} with strides {t.stride()}")
     if c is not None:
         res = c.contiguous()
     else:
-        res = out if out is not None else torch.empty((m, n), dtype=torch.float32, device=a.device)
+        res = out if out is not None else torch.empty((m, n), dtype=res_dtype, device=a.device)
     a, bt = a.contiguous(), bt.contiguous()
     if kind == "fp4":
         a, bt = a.view(torch.uint8), bt.view(torch.uint8)
@@ -314,10 +324,29 @@ def gemm_f4_check(a, bt, c, a_scale=None, bt_scale=None, inject: int = 0):
                       c.data_ptr(), m, n, k, *_scale_ptrs(a_scale, bt_scale), inject)
 
 
+def gemm_i8_nt(a, bt, out=None):
+    """``a[M,K] @ bt[N,K]^T`` in int32 on the INT8 MFMA kernel (``v_mfma_i32_32x32x32_i8``); ``a`` / ``bt`` are
+    ``int8``, M, N % 256 == 0, K % 128 == 0 and K <= 65536 (no sum of K products reaches 2^31). The result is
+    exact: the instruction's int32 accumulate, nothing added in software."""
+    a, bt, _, _, out, m, n, k, _ = _operands("gemm_i8_nt", "int8", a, bt, I8_TILE_MN, I8_TILE_K, I8_MAX_K, out=out)
+    _check(lib().amdprobe_gemm_i8_nt(a.data_ptr(), bt.data_ptr(), out.data_ptr(), m, n, k, _stream(a.device)),
+           "gemm_i8_nt")
+    return out
+
+
+def gemm_i8_check(a, bt, c, inject: int = 0):
+    """Dense check of an INT8 product ``c`` (int32) on the GPU, every element against an int32 VALU reference
+    (``v_dot4c_i32_i8``), the difference taken in integers: returns ``(sum((c - ref)^2), sum(ref^2))``, the
+    first exactly 0.0 for a correct product. M, N % 16 == 0, K % 16 == 0, K <= 1024."""
+    a, bt, _, _, c, m, n, k, _ = _operands("gemm_i8_check", "int8", a, bt, _CHECK_TILE, 16, _CHECK_MAX_K, c=c)
+    return _run_check("gemm_i8_check", lib().amdprobe_gemm_i8_check, a.device, a.data_ptr(), bt.data_ptr(),
+                      c.data_ptr(), m, n, k, inject)
+
+
 def f8_fill(buf, seed: int, kind: str = "e4m3"):
     """The FP8 / FP4 readiness operand fill into ``buf`` (byte size % 16): finite hashed ``e4m3`` / ``e5m2``
-    bytes with |x| in [0.5, 1), E8M0 block ``scale`` bytes in [124, 131], or ``e2m1``: any byte, two finite
-    FP4 codes."""
+    bytes with |x| in [0.5, 1), E8M0 block ``scale`` bytes in [124, 131], or ``e2m1`` / ``i8``: any byte (two
+    finite FP4 codes, or one int8, -128 included)."""
     if kind not in F8_FILL_KINDS:
         raise ProbeError(f"unknown f8 fill {kind!r}: {sorted(F8_FILL_KINDS)}")
     _check(lib().amdprobe_f8_fill(buf.data_ptr(), buf.numel() * buf.element_size(), seed & 0xFFFFFFFF,
@@ -327,7 +356,8 @@ def f8_fill(buf, seed: int, kind: str = "e4m3"):
 def readiness_f8(device: int = 0, seed: int = 0, mode: str = "fp8", inject: int = 0) -> float:
     """The FP8 matrix path of one device in one native call: hashed operands, the f8 MFMA GEMM (``fp8`` =
     E4M3, ``bf8`` = E5M2, ``mxfp8`` = E4M3 with E8M0 block scales through the MFMA scale inputs; ``mxfp4`` = packed E2M1 with
-    block scales on the f4 GEMM), the dense
+    block scales on the f4 GEMM; ``int8`` = any-byte int8 operands on the i8 GEMM, whose check is exact: a healthy
+    device returns 0.0), the dense
     VALU check of every element, one read-back on a private stream. Returns ``gemm_rel_err``. ``inject`` = 1
     loses a product tile, 3 skips the GEMM (tests). The GIL is released for the duration (ctypes)."""
     if mode not in READINESS_F8_MODES:

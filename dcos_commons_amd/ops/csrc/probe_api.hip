@@ -5,6 +5,7 @@
 #include "probe_kernels.hip"
 #include "f8_kernels.hip"
 #include "f4_kernels.hip"
+#include "i8_kernels.hip"
 
 #include <climits>
 #include <cmath>
@@ -97,8 +98,8 @@ AMDPROBE_EXPORT int amdprobe_pattern_check(const void* p, size_t bytes, unsigned
   return (int)hipGetLastError();
 }
 
-// The three dense checks below add sum((C - ref)^2) to out2[0] and sum(ref^2) to out2[1] (device
-// pointer, 2 floats that the caller zeroes), ref being an fp32 VALU reference of A Bt^T.
+// The four dense checks below add sum((C - ref)^2) to out2[0] and sum(ref^2) to out2[1] (device
+// pointer, 2 floats that the caller zeroes), ref being an fp32 (INT8: int32) VALU reference of A Bt^T.
 AMDPROBE_EXPORT int amdprobe_gemm_check(const void* A, const void* Bt, const float* C, int M, int N, int K,
                                         int inject, float* out2, void* stream) {
   if (const int rc = check_args(M, N, K, CHECK_TILE, 8, CHECK_MAX_K, nullptr, nullptr, {A, Bt})) return rc;
@@ -202,6 +203,24 @@ AMDPROBE_EXPORT int amdprobe_gemm_f4_check(const void* A, const void* Bt, const 
 }
 
 // ---------------------------------------------------------------------------------------
+// INT8 (i8_kernels.hip). A, Bt: int8, K bytes per row; C: int32. K <= 65536 keeps every sum below 2^31.
+// ---------------------------------------------------------------------------------------
+AMDPROBE_EXPORT int amdprobe_gemm_i8_nt(const void* A, const void* Bt, int* C, int M, int N, int K, void* stream) {
+  if (const int rc = check_args(M, N, K, i8::BM, i8::BK, i8::MAX_K, nullptr, nullptr, {A, Bt, C})) return rc;
+  hipLaunchKernelGGL(gemm_i8_nt_kernel, dim3((M / i8::BM) * (N / i8::BN)), dim3(i8::THREADS), 0, (hipStream_t)stream,
+                     (const int8_t*)A, (const int8_t*)Bt, C, M, N, K);
+  return (int)hipGetLastError();
+}
+
+AMDPROBE_EXPORT int amdprobe_gemm_i8_check(const void* A, const void* Bt, const int* C, int M, int N, int K,
+                                           int inject, float* out2, void* stream) {
+  if (const int rc = check_args(M, N, K, CHECK_TILE, 16, CHECK_MAX_K, nullptr, nullptr, {A, Bt})) return rc;
+  hipLaunchKernelGGL(gemm_i8_check_kernel, dim3((M / CHECK_TILE) * (N / CHECK_TILE)), dim3(CHECK_THREADS), 0,
+                     (hipStream_t)stream, (const int8_t*)A, (const int8_t*)Bt, C, M, N, K, inject, out2);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
 // The readiness checks: the whole check of one device in one call (see probe_kernels.hip). Buffers, a
 // non-blocking stream and a pinned result slot are created on first use per device and reused; calls
 // for one device serialize on its context, and the bf16 and f8 / f4 paths have contexts of their own
@@ -209,8 +228,8 @@ AMDPROBE_EXPORT int amdprobe_gemm_f4_check(const void* A, const void* Bt, const 
 // device is restored. Returns 0 or a HIP error / negative shape code.
 //
 // The buffers outlive the call, so a kernel that dropped its writes would leave the previous call's
-// correct data behind. Two things stop that from passing: C is poisoned with NaN bytes before the
-// GEMM, and every call mixes a per-device call counter into the seed, so the operands and the pattern
+// correct data behind. Two things stop that from passing: C is poisoned with 0xFF bytes (NaN; -1 as
+// int32) before the GEMM, and every call mixes a per-device call counter into the seed, so the operands and the pattern
 // differ from the last call's and stale data cannot match.
 // ---------------------------------------------------------------------------------------
 namespace {
@@ -331,14 +350,15 @@ AMDPROBE_EXPORT int amdprobe_readiness(int device, unsigned seed, int inject, do
 
 // The FP8 / FP4 matrix path: mode 0 = fp8 (E4M3), 1 = bf8 (E5M2), 2 = mxfp8 (E4M3 with E8M0 block
 // scales through the MFMA scale inputs), 3 = mxfp4 (packed E2M1 with block scales: the f4 GEMM and
-// check on the same buffers, half filled). Hashed operands (and scales), the GEMM, the dense VALU
+// check on the same buffers, half filled), 4 = int8 (the i8 GEMM and its exact check on the same
+// buffers: any byte is an int8, C is int32 and a healthy product gives rel_err == 0). Hashed operands (and scales), the GEMM, the dense VALU
 // check, one read-back. inject: 0 = none, 1 = lose one 16x16 tile of the product, 3 = skip the GEMM
 // launch (both must fail). There is no HBM pattern here: amdprobe_readiness does that.
 AMDPROBE_EXPORT int amdprobe_readiness_f8(int device, unsigned seed, int mode, int inject, double* rel_err) {
-  if (mode < 0 || mode > 3) return ERR_SHAPE;
+  if (mode < 0 || mode > 4) return ERR_SHAPE;
   return run_probe(g_readiness_f8, F8_BYTES, device, seed, rel_err, nullptr, [&](ProbeCtx& ctx, uint32_t call_seed) {
     hipStream_t s = ctx.stream;
-    const bool f4 = mode == 3, mx = mode >= 2;
+    const bool f4 = mode == 3, i8 = mode == 4, mx = mode == 2 || f4;
     const int fmt = mode == 1 ? F8_E5M2 : F8_E4M3;
     const size_t row_bytes = f4 ? RK / 2 : RK;
     uint8_t* scales = (uint8_t*)ctx.buf[BUF_AUX];
@@ -350,9 +370,14 @@ AMDPROBE_EXPORT int amdprobe_readiness_f8(int device, unsigned seed, int mode, i
     float* out2 = &ctx.res->diff2;
     const int lose = inject == 1 ? 1 : 0;
     PROBE_TRY(launch_fill(ctx.buf[BUF_AB], size_t(RM + RN) * row_bytes, call_seed,
-                          f4 ? FILL_E2M1 : mode == 1 ? FILL_E5M2 : FILL_E4M3, 0, ctx.res, s));
+                          f4 || i8 ? FILL_E2M1 : mode == 1 ? FILL_E5M2 : FILL_E4M3, 0, ctx.res, s));
     if (mx) PROBE_TRY(launch_fill(scales, F8_BYTES[BUF_AUX], call_seed ^ 0x5CA1E5u, FILL_SCALE, 0, nullptr, s));
-    PROBE_TRY(hipMemsetAsync(C, 0xFF, C_BYTES, s));  // NaN until the GEMM writes
+    PROBE_TRY(hipMemsetAsync(C, 0xFF, C_BYTES, s));  // NaN (int8: -1) until the GEMM writes
+    if (i8) {
+      if (inject != 3) PROBE_TRY(amdprobe_gemm_i8_nt(A, Bt, (int*)C, RM, RN, RK, s));
+      PROBE_TRY(amdprobe_gemm_i8_check(A, Bt, (const int*)C, RM, RN, RK, lose, out2, s));
+      return 0;
+    }
     if (inject != 3)
       PROBE_TRY(f4 ? amdprobe_gemm_f4_nt(A, Bt, C, RM, RN, RK, sa, sb, s)
                   : amdprobe_gemm_f8_nt(A, Bt, C, RM, RN, RK, fmt, fmt, sa, sb, s));

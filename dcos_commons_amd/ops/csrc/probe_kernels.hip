@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace amdprobe {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -483,10 +485,10 @@ void hashed_fill_kernel(uint4* __restrict__ p, size_t n16, uint32_t seed, uint32
   if (tid == 0 && res != nullptr) *res = ReadinessResult{0.f, 0.f, 0ull, 0ull};
 }
 
-// Dense check of C = A Bt^T, shared by the bf16, FP8 and FP4 check kernels: one workgroup per
+// Dense check of C = A Bt^T, shared by the bf16, FP8, FP4 and INT8 check kernels: one workgroup per
 // 16 x 16 output tile (M / 16 * N / 16 of them, so a 256 x 256 product spreads over 256 CUs).
-// The tile's 16 A rows and 16 Bt rows are staged in LDS as bytes, each thread forms the fp32
-// reference of its element on the VALU (the part that differs per format), and the workgroup
+// The tile's 16 A rows and 16 Bt rows are staged in LDS as bytes, each thread forms the fp32 (INT8:
+// int32) reference of its element on the VALU (the part that differs per format), and the workgroup
 // adds its sum of squared differences and of squared references to out2 with two float atomics
 // (out2 must arrive zeroed; the fill kernel zeroes it). Needs M, N % 16 == 0, a row of a multiple
 // of 16 bytes and K <= CHECK_MAX_K (host-checked).
@@ -533,15 +535,20 @@ __device__ __forceinline__ void check_stage_scales(const uint8_t* __restrict__ s
 
 // Compares this thread's element of C with `ref` and adds the workgroup's two sums to out2.
 // `inject` = 1 reads C[0:16][0:16] as zeros, a lost MFMA tile (tests that the check catches it).
-__device__ __forceinline__ void check_finish(const float* __restrict__ C, int N, const CheckPos& t, float ref,
-                                             int inject, float* __restrict__ out2) {
+// T is float, or int for the INT8 product: there the difference is taken in integers and only then
+// converted, so a healthy product gives d2 == 0.0f exactly.
+template <typename T>
+__device__ __forceinline__ void check_finish(const T* __restrict__ C, int N, const CheckPos& t, T ref, int inject,
+                                             float* __restrict__ out2) {
   __shared__ float red[2][CHECK_THREADS / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m = t.tm * CHECK_TILE + t.r, n = t.tn * CHECK_TILE + t.c;
-  float cv = C[(size_t)m * N + n];
-  if (inject == 1 && m < 16 && n < 16) cv = 0.f;   // a lost 16x16 tile
-  const float d = cv - ref;
-  float d2 = d * d, w2 = ref * ref;
+  T cv = C[(size_t)m * N + n];
+  if (inject == 1 && m < 16 && n < 16) cv = 0;     // a lost 16x16 tile
+  float d, w = (float)ref;
+  if constexpr (std::is_integral<T>::value) d = (float)((long long)cv - ref);
+  else d = cv - ref;
+  float d2 = d * d, w2 = w * w;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     d2 += __shfl_xor(d2, off, 64);

@@ -11,7 +11,8 @@ Runs the HIP probe kernels on one device and decides healthy / unhealthy:
   its E8M0 block-scale inputs, which the bf16 check never touches: ``ops.readiness_f8`` runs the
   f8 GEMM on hashed operands against a VALU reference of every element, per mode ``fp8`` (E4M3),
   ``bf8`` (E5M2), ``mxfp8`` (E4M3 with block scales), ``mxfp4`` (packed E2M1 with block scales: the
-  ``cbsz:4 blgp:4`` FP4 decode and nibble routing, on a kernel of its own). Same < 1e-3 bound;
+  ``cbsz:4 blgp:4`` FP4 decode and nibble routing, on a kernel of its own), ``int8`` (the integer MFMAs and
+  their int32 accumulators, the W8A8 path: exact, a healthy device gives 0). Same < 1e-3 bound;
 * **MFMA rate** -- register-resident ``v_mfma_f32_32x32x16_bf16`` loop (TFLOP/s);
 * **HBM** -- 16-B/lane streaming copy of a buffer larger than the 256 MiB Infinity Cache
   (read+write GB/s) and an address-hashed write/verify pattern (bad words must be 0).
@@ -29,7 +30,7 @@ import time
 MIN_TFLOPS = 200.0       # far below the ~2.5 PF dense peak: catches a broken/throttled matrix pipe
 MIN_HBM_GBPS = 1000.0    # far below the ~5.5 TB/s measured copy rate: catches a degraded stack
 MAX_GEMM_REL_ERR = 1e-3
-MATRIX_MODES = ("bf16", "fp8", "bf8", "mxfp8", "mxfp4")   # bf16 is always checked; the rest are opt-in
+MATRIX_MODES = ("bf16", "fp8", "bf8", "mxfp8", "mxfp4", "int8")   # bf16 is always checked; the rest are opt-in
 
 
 def _f8_modes(matrix) -> list:
@@ -44,7 +45,7 @@ def readiness_probe(device: int = 0, matrix=("bf16",)) -> dict:
     native call (``ops.readiness``): hashed bf16 operands, the MFMA GEMM, a dense fp32 check of
     every product element and the 64 MiB pattern test on a private stream with a single read-back. It sits on the deploy and
     recovery critical path of every GPU pod, and the GIL is released while it runs. Each of ``fp8``, ``bf8``,
-    ``mxfp8``, ``mxfp4`` in ``matrix`` adds one ``ops.readiness_f8`` call and a ``gemm_<mode>_rel_err`` field."""
+    ``mxfp8``, ``mxfp4``, ``int8`` in ``matrix`` adds one ``ops.readiness_f8`` call and a ``gemm_<mode>_rel_err`` field."""
     from dcos_commons_amd import ops
 
     t0 = time.perf_counter()
@@ -104,6 +105,19 @@ def run_probe(device: int = 0, quick: bool = True, matrix=("bf16",)) -> dict:
         rel8 = ops.readiness_f8(device, seed=1234 + device, mode=mode)
         report[f"gemm_{mode}_rel_err"] = rel8
         f8_ok = f8_ok and rel8 < MAX_GEMM_REL_ERR
+        if mode == "int8":
+            ab8 = torch.empty((2 * s, s), dtype=torch.int8, device=dev)
+            ops.f8_fill(ab8, seed=1234 + device, kind="i8")
+            out32 = torch.empty((s, s), dtype=torch.int32, device=dev)
+            ops.gemm_i8_nt(ab8[:s], ab8[s:], out=out32)
+            e0.record()
+            for _ in range(reps):
+                ops.gemm_i8_nt(ab8[:s], ab8[s:], out=out32)
+            e1.record()
+            e1.synchronize()
+            report["gemm_int8_tops"] = round(2.0 * s * s * s * reps / (e0.elapsed_time(e1) / 1e3) / 1e12, 1)
+            del ab8, out32
+            continue
         dt = torch.uint8 if mode == "mxfp4" else torch.float8_e5m2 if mode == "bf8" else torch.float8_e4m3fn
         ab8 = torch.empty((2 * s, s // 2 if mode == "mxfp4" else s), dtype=torch.uint8, device=dev)
         ops.f8_fill(ab8, seed=1234 + device, kind={"bf8": "e5m2", "mxfp4": "e2m1"}.get(mode, "e4m3"))
@@ -163,7 +177,7 @@ def main(argv=None) -> int:
     ap.add_argument("--full", action="store_true", help="larger shapes (slower, more precise)")
     ap.add_argument("--readiness", action="store_true", help="fast numerics + memory check only")
     ap.add_argument("--matrix", default="bf16", help="comma-separated matrix data paths to check: bf16 (always), "
-                    "fp8, bf8, mxfp8, mxfp4")
+                    "fp8, bf8, mxfp8, mxfp4, int8")
     ap.add_argument("--json", action="store_true")
     args = ap.parse_args(argv)
     matrix = tuple(m for m in args.matrix.split(",") if m)
