@@ -1,12 +1,14 @@
 """MI355X device ops: HIP probe kernels behind a torch-tensor API.
 
-The kernels live in four files under ``csrc/``:
+The kernels live in five files under ``csrc/``:
 
 * ``probe_kernels.hip``: MFMA bf16 GEMM, MFMA issue-rate loop, HBM streaming copy, HBM pattern test,
   the hashed operand fill and the shared parts of the dense VALU check;
 * ``f8_kernels.hip``: FP8 / MXFP8 MFMA GEMM and its check;
 * ``f4_kernels.hip``: FP4 / MXFP4 MFMA GEMM and its check;
-* ``i8_kernels.hip``: INT8 MFMA GEMM (int32 accumulators) and its exact check.
+* ``i8_kernels.hip``: INT8 MFMA GEMM (int32 accumulators) and its exact check;
+* ``f64_kernels.hip``: FP64 MFMA GEMM (``v_mfma_f64_16x16x4_f64``, fp64 accumulators), its check, which
+  subtracts in fp64, and the hashed fp64 operand fill.
 
 They are compiled for gfx950 into the in-tree ``_amdprobe.so`` (``python -m dcos_commons_amd.ops.build``)
 and back the GPU readiness/health check that gates pods which request ``gpus``
@@ -63,6 +65,8 @@ def _bind(lib: ctypes.CDLL) -> None:
             ("gemm_f4_check", i, [vp, vp, vp, i, i, i, vp, vp, i, vp, vp]),
             ("gemm_i8_nt", i, [vp, vp, vp, i, i, i, vp]),
             ("gemm_i8_check", i, [vp, vp, vp, i, i, i, i, vp, vp]),
+            ("gemm_f64_nt", i, [vp, vp, vp, i, i, i, vp]),
+            ("gemm_f64_check", i, [vp, vp, vp, i, i, i, i, vp, vp]),
             ("readiness_f8", i, [i, u, i, i, pd])):
         fn = getattr(lib, "amdprobe_" + name)
         fn.restype = restype
@@ -100,15 +104,21 @@ def _check(rc: int, what: str) -> None:
 
 F8_TILE = 128                       # M, N and K granule of gemm_f8_nt
 F8_BLOCK = 32                       # K elements per E8M0 block scale
-F8_FILL_KINDS = {"e4m3": 0, "e5m2": 1, "scale": 2, "e2m1": 3, "i8": 3}   # i8: the any-byte fill
-READINESS_F8_MODES = {"fp8": 0, "bf8": 1, "mxfp8": 2, "mxfp4": 3, "int8": 4}
+F8_FILL_KINDS = {"e4m3": 0, "e5m2": 1, "scale": 2, "e2m1": 3, "i8": 3, "f64": 5}   # i8: the any-byte fill
+READINESS_F8_MODES = {"fp8": 0, "bf8": 1, "mxfp8": 2, "mxfp4": 3, "int8": 4, "fp64": 5}
 F4_TILE_MN = 256                    # M and N granule of gemm_f4_nt
 F4_TILE_K = 256                     # K granule (elements) of gemm_f4_nt
 I8_TILE_MN = 256                    # M and N granule of gemm_i8_nt
 I8_TILE_K = 128                     # K granule of gemm_i8_nt
 I8_MAX_K = 65536                    # its largest K: no int32 sum of K products can wrap
+F64_TILE_M = 256                    # M granule of gemm_f64_nt
+F64_TILE_N = 128                    # its N granule
+F64_TILE_K = 16                     # its K granule (one 128-byte row of doubles)
+F64_RING = 3                        # K-tiles in its LDS ring
+READINESS_F64_SHAPE = (256, 256, 128)   # M, N, K of the fp64 readiness GEMM (csrc/probe_api.hip)
 _CHECK_TILE = 16                    # M and N granule of the dense checks
 _CHECK_MAX_K = 1024                 # their largest K (one tile's operand rows sit in LDS)
+_CHECK_F64_MAX_K = 256              # the fp64 check's: its rows are 8 * K bytes
 
 
 def _operands(what: str, kind: str, a, bt, granule: int, k_granule: int, k_max=None, a_scale=None, bt_scale=None,
@@ -116,7 +126,7 @@ def _operands(what: str, kind: str, a, bt, granule: int, k_granule: int, k_max=N
     """Validates the operands of a GEMM or check wrapper before native code sees their pointers; returns
     ``(a, bt, a_scale, bt_scale, res, m, n, k, fmt)`` with contiguous tensors. ``kind`` is ``bf16``, ``fp8``
     (``fmt`` = the two format codes of the native call, else ``()``), ``int8`` (the product is int32, not
-    float32) or ``fp4`` (packed: K is twice the row length; the operands come back as uint8). ``res`` is the product: ``c`` made contiguous when the caller
+    float32), ``fp64`` (float64 operands and product; ``granule`` may be an ``(M, N)`` pair) or ``fp4`` (packed: K is twice the row length; the operands come back as uint8). ``res`` is the product: ``c`` made contiguous when the caller
     has one to check, else ``out``, allocated when ``None``. Shape, granule, dtype and paired-scale errors
     are reported first; then every tensor must be on the operands' one GPU, and the product a float32
     ``(m, n)``, a caller's ``out`` contiguous as well (the kernel writes through its pointer)."""
@@ -134,6 +144,8 @@ def _operands(what: str, kind: str, a, bt, granule: int, k_granule: int, k_max=N
                 raise ProbeError(f"{what}: E5M2 x E4M3 is not built (swap the operands: E4M3 x E5M2 is)")
     elif kind == "int8":
         ok, expects = a.dtype == bt.dtype == torch.int8, "int8"
+    elif kind == "fp64":
+        ok, expects = a.dtype == bt.dtype == torch.float64, "float64"
     else:
         packed = (torch.uint8, getattr(torch, "float4_e2m1fn_x2", torch.uint8))
         ok, expects = a.dtype in packed and bt.dtype in packed, "packed E2M1 (uint8 or float4_e2m1fn_x2)"
@@ -143,7 +155,8 @@ def _operands(what: str, kind: str, a, bt, granule: int, k_granule: int, k_max=N
         raise ProbeError(f"{what} shape mismatch: {tuple(a.shape)} x {tuple(bt.shape)}^T"
                          f"{' (packed, K/2 bytes per row)' if kind == 'fp4' else ''}")
     m, n, k = a.shape[0], bt.shape[0], a.shape[1] * (2 if kind == "fp4" else 1)
-    if m % granule or n % granule or k % k_granule or m == 0 or n == 0 or k == 0 or (k_max and k > k_max):
+    gm, gn = granule if isinstance(granule, tuple) else (granule, granule)
+    if m % gm or n % gn or k % k_granule or m == 0 or n == 0 or k == 0 or (k_max and k > k_max):
         raise ProbeError(f"{what} needs M,N % {granule} == 0 and K % {k_granule} == 0"
                          f"{f' and K <= {k_max}' if k_max else ''}, got {m}x{n}x{k}")
     if (a_scale is None) != (bt_scale is None):
@@ -158,7 +171,7 @@ def _operands(what: str, kind: str, a, bt, granule: int, k_granule: int, k_max=N
     for name, t in (("a", a), ("bt", bt), ("a_scale", a_scale), ("bt_scale", bt_scale), ("out", out), ("c", c)):
         if t is not None and (t.device.type != "cuda" or t.device != a.device):
             raise ProbeError(f"{what}: {name} is on {t.device}; all operands must be on one GPU (a is on {a.device})")
-    res_dtype = torch.int32 if kind == "int8" else torch.float32
+    res_dtype = torch.int32 if kind == "int8" else torch.float64 if kind == "fp64" else torch.float32
     for name, t in (("out", out), ("c", c)):
         if t is not None and (t.dtype != res_dtype or tuple(t.shape) != (m, n) or
                               (t is out and not t.is_contiguous())):
@@ -343,10 +356,31 @@ def gemm_i8_check(a, bt, c, inject: int = 0):
                       c.data_ptr(), m, n, k, inject)
 
 
+def gemm_f64_nt(a, bt, out=None):
+    """``a[M,K] @ bt[N,K]^T`` in fp64 on the FP64 MFMA kernel (``v_mfma_f64_16x16x4_f64``); ``a`` / ``bt`` are
+    ``float64``, M % 256 == 0, N % 128 == 0, K % 16 == 0. Every product and sum is the instruction's; the
+    result differs from a sequential sum only in summation order."""
+    a, bt, _, _, out, m, n, k, _ = _operands("gemm_f64_nt", "fp64", a, bt, (F64_TILE_M, F64_TILE_N), F64_TILE_K,
+                                             out=out)
+    _check(lib().amdprobe_gemm_f64_nt(a.data_ptr(), bt.data_ptr(), out.data_ptr(), m, n, k, _stream(a.device)),
+           "gemm_f64_nt")
+    return out
+
+
+def gemm_f64_check(a, bt, c, inject: int = 0):
+    """Dense check of an FP64 product ``c`` (float64) on the GPU, every element against an fp64 VALU reference
+    (``v_fma_f64``), the difference taken in fp64 before it is narrowed: returns ``(sum((c - ref)^2),
+    sum(ref^2))`` as float32 sums. M, N % 16 == 0, K % 4 == 0, K <= 256."""
+    a, bt, _, _, c, m, n, k, _ = _operands("gemm_f64_check", "fp64", a, bt, _CHECK_TILE, 4, _CHECK_F64_MAX_K, c=c)
+    return _run_check("gemm_f64_check", lib().amdprobe_gemm_f64_check, a.device, a.data_ptr(), bt.data_ptr(),
+                      c.data_ptr(), m, n, k, inject)
+
+
 def f8_fill(buf, seed: int, kind: str = "e4m3"):
     """The FP8 / FP4 readiness operand fill into ``buf`` (byte size % 16): finite hashed ``e4m3`` / ``e5m2``
-    bytes with |x| in [0.5, 1), E8M0 block ``scale`` bytes in [124, 131], or ``e2m1`` / ``i8``: any byte (two
-    finite FP4 codes, or one int8, -128 included)."""
+    bytes with |x| in [0.5, 1), E8M0 block ``scale`` bytes in [124, 131], ``e2m1`` / ``i8``: any byte (two
+    finite FP4 codes, or one int8, -128 included), or ``f64``: finite doubles with a hashed sign, |x| in
+    [0.5, 1) and all 52 mantissa bits hashed."""
     if kind not in F8_FILL_KINDS:
         raise ProbeError(f"unknown f8 fill {kind!r}: {sorted(F8_FILL_KINDS)}")
     _check(lib().amdprobe_f8_fill(buf.data_ptr(), buf.numel() * buf.element_size(), seed & 0xFFFFFFFF,
@@ -357,7 +391,9 @@ def readiness_f8(device: int = 0, seed: int = 0, mode: str = "fp8", inject: int 
     """The FP8 matrix path of one device in one native call: hashed operands, the f8 MFMA GEMM (``fp8`` =
     E4M3, ``bf8`` = E5M2, ``mxfp8`` = E4M3 with E8M0 block scales through the MFMA scale inputs; ``mxfp4`` = packed E2M1 with
     block scales on the f4 GEMM; ``int8`` = any-byte int8 operands on the i8 GEMM, whose check is exact: a healthy
-    device returns 0.0), the dense
+    device returns 0.0;
+    ``fp64`` = hashed doubles on the f64 GEMM at 256 x 256 x 128, checked in fp64: judge it by
+    ``gpu_health.MAX_GEMM_F64_REL_ERR``), the dense
     VALU check of every element, one read-back on a private stream. Returns ``gemm_rel_err``. ``inject`` = 1
     loses a product tile, 3 skips the GEMM (tests). The GIL is released for the duration (ctypes)."""
     if mode not in READINESS_F8_MODES:

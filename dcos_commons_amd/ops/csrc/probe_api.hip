@@ -6,6 +6,7 @@
 #include "f8_kernels.hip"
 #include "f4_kernels.hip"
 #include "i8_kernels.hip"
+#include "f64_kernels.hip"
 
 #include <climits>
 #include <cmath>
@@ -126,9 +127,22 @@ AMDPROBE_EXPORT int amdprobe_readiness_fill(void* ab, size_t ab_bytes, unsigned 
   return launch_fill(ab, ab_bytes, seed, FILL_BF16, 64, res, stream);
 }
 
+// The fp64 fill (hashed_fill_f64_kernel), with launch_fill's contract.
+static int launch_fill_f64(void* p, size_t bytes, unsigned seed, void* res, void* stream) {
+  if (bytes == 0 || bytes % 16) return ERR_SHAPE;
+  if (!aligned16(p) || !aligned16(res)) return ERR_ALIGN;
+  const size_t n16 = bytes / 16;
+  const int blocks = (int)((n16 + 255) / 256 < 1024 ? (n16 + 255) / 256 : 1024);
+  hipLaunchKernelGGL(hashed_fill_f64_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (uint4*)p, n16,
+                     (uint32_t)seed, (ReadinessResult*)res);
+  return (int)hipGetLastError();
+}
+
 // The FP8 / FP4 readiness fill: kind 0 = E4M3 bytes, 1 = E5M2 bytes, 2 = E8M0 block scales, 3 = packed
-// E2M1 nibbles (see hashed_fill_kernel). `res` may be null; otherwise see launch_fill.
+// E2M1 nibbles (see hashed_fill_kernel), 5 = fp64 (hashed_fill_f64_kernel). `res` may be null; otherwise
+// see launch_fill.
 AMDPROBE_EXPORT int amdprobe_f8_fill(void* p, size_t bytes, unsigned seed, int kind, float* res, void* stream) {
+  if (kind == FILL_F64) return launch_fill_f64(p, bytes, seed, res, stream);
   return kind > FILL_E2M1 ? (int)ERR_SHAPE : launch_fill(p, bytes, seed, kind, 0, res, stream);
 }
 
@@ -221,9 +235,29 @@ AMDPROBE_EXPORT int amdprobe_gemm_i8_check(const void* A, const void* Bt, const 
 }
 
 // ---------------------------------------------------------------------------------------
+// FP64 (f64_kernels.hip). A, Bt: doubles, 8 * K bytes per row; C: fp64. M % 256, N % 128, K % 16.
+// ---------------------------------------------------------------------------------------
+AMDPROBE_EXPORT int amdprobe_gemm_f64_nt(const void* A, const void* Bt, double* C, int M, int N, int K, void* stream) {
+  if (const int rc = check_args(M, N, K, f64::BN, f64::BK, INT_MAX, nullptr, nullptr, {A, Bt, C})) return rc;
+  if (M % f64::BM) return ERR_SHAPE;
+  hipLaunchKernelGGL(gemm_f64_nt_kernel, dim3((M / f64::BM) * (N / f64::BN)), dim3(f64::THREADS), 0,
+                     (hipStream_t)stream, (const double*)A, (const double*)Bt, C, M, N, K);
+  return (int)hipGetLastError();
+}
+
+AMDPROBE_EXPORT int amdprobe_gemm_f64_check(const void* A, const void* Bt, const double* C, int M, int N, int K,
+                                            int inject, float* out2, void* stream) {
+  if (const int rc = check_args(M, N, K, CHECK_TILE, 4, f64::CHECK_MAX_K, nullptr, nullptr, {A, Bt})) return rc;
+  hipLaunchKernelGGL(gemm_f64_check_kernel, dim3((M / CHECK_TILE) * (N / CHECK_TILE)), dim3(CHECK_THREADS), 0,
+                     (hipStream_t)stream, (const double*)A, (const double*)Bt, C, M, N, K, inject, out2);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
 // The readiness checks: the whole check of one device in one call (see probe_kernels.hip). Buffers, a
 // non-blocking stream and a pinned result slot are created on first use per device and reused; calls
 // for one device serialize on its context, and the bf16 and f8 / f4 paths have contexts of their own
+// and so has fp64
 // (they neither wait for each other nor allocate each other's buffers). The calling thread's current
 // device is restored. Returns 0 or a HIP error / negative shape code.
 //
@@ -248,9 +282,14 @@ struct ProbeCtx {
   ReadinessResult* host = nullptr;  // pinned
   uint32_t calls = 0;               // mixed into the seed: no two calls share operands or pattern
 };
-ProbeCtx g_readiness[MAX_DEVICES], g_readiness_f8[MAX_DEVICES];
+ProbeCtx g_readiness[MAX_DEVICES], g_readiness_f8[MAX_DEVICES], g_readiness_f64[MAX_DEVICES];
 constexpr size_t BF16_BYTES[PROBE_BUFS] = {size_t(RM + RN) * RK * sizeof(__bf16), C_BYTES, PATTERN_BYTES};
 constexpr size_t F8_BYTES[PROBE_BUFS] = {size_t(RM + RN) * RK, C_BYTES, size_t(RM + RN) * (RK / 32)};
+// fp64: K = 128 is 8 K-tiles of 16, so the three-stage ring of gemm_f64_nt_kernel reaches its steady state
+// (it needs ring depth + 2 = 5), and the 256 x 256 product is two of its 256 x 128 workgroups. No aux buffer is
+// used; the slot gets 16 bytes.
+constexpr int RK64 = 128;
+constexpr size_t F64_BYTES[PROBE_BUFS] = {size_t(RM + RN) * RK64 * sizeof(double), size_t(RM) * RN * sizeof(double), 16};
 
 struct DeviceGuard {
   int prev = -1;
@@ -354,8 +393,22 @@ AMDPROBE_EXPORT int amdprobe_readiness(int device, unsigned seed, int inject, do
 // buffers: any byte is an int8, C is int32 and a healthy product gives rel_err == 0). Hashed operands (and scales), the GEMM, the dense VALU
 // check, one read-back. inject: 0 = none, 1 = lose one 16x16 tile of the product, 3 = skip the GEMM
 // launch (both must fail). There is no HBM pattern here: amdprobe_readiness does that.
+// Mode 5 = fp64 runs on a context and buffers of its own (8-byte operands and product do not fit F8_BYTES):
+// hashed doubles, C poisoned with 0xFF bytes (a double NaN), the f64 GEMM, its fp64 check, one read-back.
 AMDPROBE_EXPORT int amdprobe_readiness_f8(int device, unsigned seed, int mode, int inject, double* rel_err) {
-  if (mode < 0 || mode > 4) return ERR_SHAPE;
+  if (mode < 0 || mode > 5) return ERR_SHAPE;
+  if (mode == 5)
+    return run_probe(g_readiness_f64, F64_BYTES, device, seed, rel_err, nullptr, [&](ProbeCtx& ctx, uint32_t call_seed) {
+      hipStream_t s = ctx.stream;
+      const double* A = (const double*)ctx.buf[BUF_AB];
+      const double* Bt = A + size_t(RM) * RK64;
+      double* C = (double*)ctx.buf[BUF_C];
+      PROBE_TRY(launch_fill_f64(ctx.buf[BUF_AB], F64_BYTES[BUF_AB], call_seed, ctx.res, s));
+      PROBE_TRY(hipMemsetAsync(C, 0xFF, F64_BYTES[BUF_C], s));  // NaN until the GEMM writes
+      if (inject != 3) PROBE_TRY(amdprobe_gemm_f64_nt(A, Bt, C, RM, RN, RK64, s));
+      PROBE_TRY(amdprobe_gemm_f64_check(A, Bt, C, RM, RN, RK64, inject == 1 ? 1 : 0, &ctx.res->diff2, s));
+      return 0;
+    });
   return run_probe(g_readiness_f8, F8_BYTES, device, seed, rel_err, nullptr, [&](ProbeCtx& ctx, uint32_t call_seed) {
     hipStream_t s = ctx.stream;
     const bool f4 = mode == 3, i8 = mode == 4, mx = mode == 2 || f4;

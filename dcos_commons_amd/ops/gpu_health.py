@@ -13,6 +13,10 @@ Runs the HIP probe kernels on one device and decides healthy / unhealthy:
   ``bf8`` (E5M2), ``mxfp8`` (E4M3 with block scales), ``mxfp4`` (packed E2M1 with block scales: the
   ``cbsz:4 blgp:4`` FP4 decode and nibble routing, on a kernel of its own), ``int8`` (the integer MFMAs and
   their int32 accumulators, the W8A8 path: exact, a healthy device gives 0). Same < 1e-3 bound;
+* **FP64 MFMA numerics** (opt-in, ``fp64``) -- ``v_mfma_f64_16x16x4_f64`` and its fp64 accumulators, the
+  path HPC payloads run on: the f64 GEMM on hashed doubles against an fp64 VALU reference, the difference
+  taken in fp64. Its bound is ``MAX_GEMM_F64_REL_ERR`` = 1e-10, not 1e-3: a product silently computed at
+  single precision (2^-24) must fail;
 * **MFMA rate** -- register-resident ``v_mfma_f32_32x32x16_bf16`` loop (TFLOP/s);
 * **HBM** -- 16-B/lane streaming copy of a buffer larger than the 256 MiB Infinity Cache
   (read+write GB/s) and an address-hashed write/verify pattern (bad words must be 0).
@@ -30,7 +34,19 @@ import time
 MIN_TFLOPS = 200.0       # far below the ~2.5 PF dense peak: catches a broken/throttled matrix pipe
 MIN_HBM_GBPS = 1000.0    # far below the ~5.5 TB/s measured copy rate: catches a degraded stack
 MAX_GEMM_REL_ERR = 1e-3
-MATRIX_MODES = ("bf16", "fp8", "bf8", "mxfp8", "mxfp4", "int8")   # bf16 is always checked; the rest are opt-in
+# The fp64 mode's own bound, for the readiness K of 128 (ops.READINESS_F64_SHAPE). It sits between two levels.
+# Healthy: the GEMM and the VALU reference are both fp64 sums of K terms in different orders, each within
+# K * 2^-53 * sum|a||b| of exact; for the hashed fill (mixed signs, |x| in [0.5, 1)) the norm of sum|a||b| over
+# the norm of sum(ab) is about sqrt(K), so the relative Frobenius error is at most about 2 * K^1.5 * 2^-53,
+# 3e-13 at K = 128. Faulty: a product rounded once through fp32 is off by about 2^-24 = 6e-8 per element, which
+# the shared 1e-3 would pass. 1e-10 is near the geometric middle of the two (1.4e-10).
+MAX_GEMM_F64_REL_ERR = 1e-10
+# bf16 is always checked; the rest are opt-in
+MATRIX_MODES = ("bf16", "fp8", "bf8", "mxfp8", "mxfp4", "int8", "fp64")
+
+
+def _max_rel_err(mode: str) -> float:
+    return MAX_GEMM_F64_REL_ERR if mode == "fp64" else MAX_GEMM_REL_ERR
 
 
 def _f8_modes(matrix) -> list:
@@ -45,7 +61,7 @@ def readiness_probe(device: int = 0, matrix=("bf16",)) -> dict:
     native call (``ops.readiness``): hashed bf16 operands, the MFMA GEMM, a dense fp32 check of
     every product element and the 64 MiB pattern test on a private stream with a single read-back. It sits on the deploy and
     recovery critical path of every GPU pod, and the GIL is released while it runs. Each of ``fp8``, ``bf8``,
-    ``mxfp8``, ``mxfp4``, ``int8`` in ``matrix`` adds one ``ops.readiness_f8`` call and a ``gemm_<mode>_rel_err`` field."""
+    ``mxfp8``, ``mxfp4``, ``int8``, ``fp64`` in ``matrix`` adds one ``ops.readiness_f8`` call and a ``gemm_<mode>_rel_err`` field."""
     from dcos_commons_amd import ops
 
     t0 = time.perf_counter()
@@ -55,7 +71,7 @@ def readiness_probe(device: int = 0, matrix=("bf16",)) -> dict:
     for mode in _f8_modes(matrix):
         rel8 = ops.readiness_f8(device, seed=4321 + device, mode=mode)
         rep[f"gemm_{mode}_rel_err"] = rel8
-        healthy = healthy and rel8 < MAX_GEMM_REL_ERR
+        healthy = healthy and rel8 < _max_rel_err(mode)
     rep["healthy"] = bool(healthy)
     rep["probe_seconds"] = round(time.perf_counter() - t0, 4)
     return rep
@@ -104,7 +120,7 @@ def run_probe(device: int = 0, quick: bool = True, matrix=("bf16",)) -> dict:
         # numerics through the native check (hashed operands), throughput on the same square shape
         rel8 = ops.readiness_f8(device, seed=1234 + device, mode=mode)
         report[f"gemm_{mode}_rel_err"] = rel8
-        f8_ok = f8_ok and rel8 < MAX_GEMM_REL_ERR
+        f8_ok = f8_ok and rel8 < _max_rel_err(mode)
         if mode == "int8":
             ab8 = torch.empty((2 * s, s), dtype=torch.int8, device=dev)
             ops.f8_fill(ab8, seed=1234 + device, kind="i8")
@@ -117,6 +133,19 @@ def run_probe(device: int = 0, quick: bool = True, matrix=("bf16",)) -> dict:
             e1.synchronize()
             report["gemm_int8_tops"] = round(2.0 * s * s * s * reps / (e0.elapsed_time(e1) / 1e3) / 1e12, 1)
             del ab8, out32
+            continue
+        if mode == "fp64":
+            ab64 = torch.empty((2 * s, s), dtype=torch.float64, device=dev)
+            ops.f8_fill(ab64, seed=1234 + device, kind="f64")
+            out64 = torch.empty((s, s), dtype=torch.float64, device=dev)
+            ops.gemm_f64_nt(ab64[:s], ab64[s:], out=out64)
+            e0.record()
+            for _ in range(reps):
+                ops.gemm_f64_nt(ab64[:s], ab64[s:], out=out64)
+            e1.record()
+            e1.synchronize()
+            report["gemm_fp64_tflops"] = round(2.0 * s * s * s * reps / (e0.elapsed_time(e1) / 1e3) / 1e12, 1)
+            del ab64, out64
             continue
         dt = torch.uint8 if mode == "mxfp4" else torch.float8_e5m2 if mode == "bf8" else torch.float8_e4m3fn
         ab8 = torch.empty((2 * s, s // 2 if mode == "mxfp4" else s), dtype=torch.uint8, device=dev)
@@ -177,7 +206,7 @@ def main(argv=None) -> int:
     ap.add_argument("--full", action="store_true", help="larger shapes (slower, more precise)")
     ap.add_argument("--readiness", action="store_true", help="fast numerics + memory check only")
     ap.add_argument("--matrix", default="bf16", help="comma-separated matrix data paths to check: bf16 (always), "
-                    "fp8, bf8, mxfp8, mxfp4, int8")
+                    "fp8, bf8, mxfp8, mxfp4, int8, fp64")
     ap.add_argument("--json", action="store_true")
     args = ap.parse_args(argv)
     matrix = tuple(m for m in args.matrix.split(",") if m)
