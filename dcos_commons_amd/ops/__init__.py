@@ -1,6 +1,6 @@
 """MI355X device ops: HIP probe kernels behind a torch-tensor API.
 
-The kernels live in five files under ``csrc/``:
+The kernels live in six files under ``csrc/``:
 
 * ``probe_kernels.hip``: MFMA bf16 GEMM, MFMA issue-rate loop, HBM streaming copy, HBM pattern test,
   the hashed operand fill and the shared parts of the dense VALU check;
@@ -8,7 +8,10 @@ The kernels live in five files under ``csrc/``:
 * ``f4_kernels.hip``: FP4 / MXFP4 MFMA GEMM and its check;
 * ``i8_kernels.hip``: INT8 MFMA GEMM (int32 accumulators) and its exact check;
 * ``f64_kernels.hip``: FP64 MFMA GEMM (``v_mfma_f64_16x16x4_f64``, fp64 accumulators), its check, which
-  subtracts in fp64, and the hashed fp64 operand fill.
+  subtracts in fp64, and the hashed fp64 operand fill;
+* ``sp_kernels.hip``: 2:4 sparse bf16 MFMA GEMM (``v_smfmac_f32_16x16x64_bf16``) on a compressed A, the VALU
+  expansion of a compressed A to dense (the dense bf16 check then serves as its reference) and the hashed
+  metadata fill.
 
 They are compiled for gfx950 into the in-tree ``_amdprobe.so`` (``python -m dcos_commons_amd.ops.build``)
 and back the GPU readiness/health check that gates pods which request ``gpus``
@@ -67,6 +70,8 @@ def _bind(lib: ctypes.CDLL) -> None:
             ("gemm_i8_check", i, [vp, vp, vp, i, i, i, i, vp, vp]),
             ("gemm_f64_nt", i, [vp, vp, vp, i, i, i, vp]),
             ("gemm_f64_check", i, [vp, vp, vp, i, i, i, i, vp, vp]),
+            ("gemm_sp_bf16_nt", i, [vp, vp, vp, vp, i, i, i, vp]),
+            ("sp24_expand", i, [vp, vp, vp, i, i, vp]),
             ("readiness_f8", i, [i, u, i, i, pd])):
         fn = getattr(lib, "amdprobe_" + name)
         fn.restype = restype
@@ -104,8 +109,8 @@ def _check(rc: int, what: str) -> None:
 
 F8_TILE = 128                       # M, N and K granule of gemm_f8_nt
 F8_BLOCK = 32                       # K elements per E8M0 block scale
-F8_FILL_KINDS = {"e4m3": 0, "e5m2": 1, "scale": 2, "e2m1": 3, "i8": 3, "f64": 5}   # i8: the any-byte fill
-READINESS_F8_MODES = {"fp8": 0, "bf8": 1, "mxfp8": 2, "mxfp4": 3, "int8": 4, "fp64": 5}
+F8_FILL_KINDS = {"e4m3": 0, "e5m2": 1, "scale": 2, "e2m1": 3, "i8": 3, "f64": 5, "meta24": 6}   # i8: the any-byte fill
+READINESS_F8_MODES = {"fp8": 0, "bf8": 1, "mxfp8": 2, "mxfp4": 3, "int8": 4, "fp64": 5, "sparse24": 6}
 F4_TILE_MN = 256                    # M and N granule of gemm_f4_nt
 F4_TILE_K = 256                     # K granule (elements) of gemm_f4_nt
 I8_TILE_MN = 256                    # M and N granule of gemm_i8_nt
@@ -116,6 +121,11 @@ F64_TILE_N = 128                    # its N granule
 F64_TILE_K = 16                     # its K granule (one 128-byte row of doubles)
 F64_RING = 3                        # K-tiles in its LDS ring
 READINESS_F64_SHAPE = (256, 256, 128)   # M, N, K of the fp64 readiness GEMM (csrc/probe_api.hip)
+SP_TILE_M = 256                     # M granule of gemm_sp_bf16_nt
+SP_TILE_N = 128                     # its N granule
+SP_TILE_K = 128                     # its K granule, in dense K elements (64 compressed values, 16 metadata bytes)
+SP_RING = 2                         # K-tiles in its LDS ring (held as four half-tile stages)
+READINESS_SP_SHAPE = (256, 256, 512)    # M, N, dense K of the sparse24 readiness GEMM (csrc/probe_api.hip)
 _CHECK_TILE = 16                    # M and N granule of the dense checks
 _CHECK_MAX_K = 1024                 # their largest K (one tile's operand rows sit in LDS)
 _CHECK_F64_MAX_K = 256              # the fp64 check's: its rows are 8 * K bytes
@@ -376,11 +386,96 @@ def gemm_f64_check(a, bt, c, inject: int = 0):
                       c.data_ptr(), m, n, k, inject)
 
 
+def _sp_operands(what: str, a_vals, a_meta, others=()):
+    """Validates a compressed 2:4 pair before native code sees a pointer; returns ``(a_vals, a_meta, m, k)``,
+    contiguous, ``k`` the dense K. Dtypes and shapes first; then ``a_vals``, ``a_meta`` and every ``(name,
+    tensor)`` of ``others`` must be on one GPU. Tensor contents are never read."""
+    import torch
+
+    if a_vals.dtype != torch.bfloat16 or a_meta.dtype != torch.uint8:
+        raise ProbeError(f"{what} expects bfloat16 a_vals and uint8 a_meta, got {a_vals.dtype} and {a_meta.dtype}")
+    if a_vals.dim() != 2 or a_vals.shape[0] == 0 or a_vals.shape[1] == 0 or a_vals.shape[1] % 4:
+        raise ProbeError(f"{what}: a_vals must be [M, K/2] with K % 8 == 0, got {tuple(a_vals.shape)}")
+    m, k = a_vals.shape[0], 2 * a_vals.shape[1]
+    if tuple(a_meta.shape) != (m, k // 8):
+        raise ProbeError(f"{what}: a_meta must be [M, K/8] = {(m, k // 8)} for a_vals {tuple(a_vals.shape)}, got "
+                         f"{tuple(a_meta.shape)}")
+    for name, t in (("a_vals", a_vals), ("a_meta", a_meta)) + tuple(others):
+        if t is not None and (t.device.type != "cuda" or t.device != a_vals.device):
+            raise ProbeError(f"{what}: {name} is on {t.device}; all operands must be on one GPU (a_vals is on "
+                             f"{a_vals.device})")
+    return a_vals.contiguous(), a_meta.contiguous(), m, k
+
+
+def gemm_sp_bf16_nt(a_vals, a_meta, bt, out=None):
+    """``A[M,K] @ bt[N,K]^T`` in fp32 on the 2:4 sparse MFMA kernel (``v_smfmac_f32_16x16x64_bf16``), A given
+    compressed; M % 256 == 0, N % 128 == 0, K % 128 == 0. ``a_vals[M, K/2]`` (bfloat16): values ``2g`` and
+    ``2g + 1`` of a row are the first and second kept element, in increasing K, of its group ``g`` of four
+    consecutive K. ``a_meta[M, K/8]`` (uint8): byte ``j`` holds group ``2j`` in bits 3:0 and group ``2j + 1`` in
+    bits 7:4; in a nibble bits 1:0 are the position (0..3) of the first kept element and bits 3:2 of the second,
+    first < second (the legal nibbles are 4, 8, 12, 9, 13, 14; kept values may be zero). ``bt[N, K]`` is dense
+    bfloat16. The wrappers do not read tensor contents, so nibble legality is not checked: an illegal nibble
+    gives a wrong product, never an out-of-bounds access. ``sp24_compress`` makes the pair from a dense matrix."""
+    import torch
+
+    what = "gemm_sp_bf16_nt"
+    if a_vals.dtype != torch.bfloat16 or bt.dtype != torch.bfloat16 or a_meta.dtype != torch.uint8:
+        raise ProbeError(f"{what} expects bfloat16 a_vals and bt and a uint8 a_meta, got {a_vals.dtype}, {bt.dtype} "
+                         f"and {a_meta.dtype}")
+    if bt.dim() != 2 or a_vals.dim() != 2 or bt.shape[1] != 2 * a_vals.shape[1]:
+        raise ProbeError(f"{what} shape mismatch: a_vals {tuple(a_vals.shape)} (K/2 per row) x bt {tuple(bt.shape)}^T")
+    n = bt.shape[0]
+    if a_vals.shape[0] % SP_TILE_M or n % SP_TILE_N or bt.shape[1] % SP_TILE_K or n == 0 or bt.shape[1] == 0:
+        raise ProbeError(f"{what} needs M % {SP_TILE_M} == 0, N % {SP_TILE_N} == 0 and K % {SP_TILE_K} == 0, got "
+                         f"{a_vals.shape[0]}x{n}x{bt.shape[1]}")
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (a_vals.shape[0], n)):
+        raise ProbeError(f"{what}: out must be a contiguous float32 {(a_vals.shape[0], n)}, got {out.dtype} "
+                         f"{tuple(out.shape)}")
+    a_vals, a_meta, m, k = _sp_operands(what, a_vals, a_meta, (("bt", bt), ("out", out)))
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.float32, device=a_vals.device)
+    elif not out.is_contiguous():
+        raise ProbeError(f"{what}: out must be contiguous, got strides {out.stride()}")
+    _check(lib().amdprobe_gemm_sp_bf16_nt(a_vals.data_ptr(), a_meta.data_ptr(), bt.contiguous().data_ptr(),
+                                          out.data_ptr(), m, n, k, _stream(a_vals.device)), what)
+    return out
+
+
+def sp24_expand(a_vals, a_meta):
+    """The dense bfloat16 ``A[M, K]`` of a compressed pair (format: ``gemm_sp_bf16_nt``), on the GPU with VALU
+    code only: every element that the metadata does not name is zero. Nibble legality is not checked."""
+    import torch
+
+    a_vals, a_meta, m, k = _sp_operands("sp24_expand", a_vals, a_meta)
+    a = torch.empty((m, k), dtype=torch.bfloat16, device=a_vals.device)
+    _check(lib().amdprobe_sp24_expand(a_vals.data_ptr(), a_meta.data_ptr(), a.data_ptr(), m, k,
+                                      _stream(a_vals.device)), "sp24_expand")
+    return a
+
+
+def sp24_compress(a):
+    """``(a_vals, a_meta)`` of a dense ``a[M, K]`` (K % 8 == 0) in the format of ``gemm_sp_bf16_nt``: of every
+    group of four consecutive K the two elements of largest magnitude are kept, ties going to the lower
+    position. Plain torch on ``a``'s device: plumbing for tests and tools, not a hot path."""
+    import torch
+
+    if a.dim() != 2 or a.shape[1] == 0 or a.shape[1] % 8:
+        raise ProbeError(f"sp24_compress needs a [M, K] with K % 8 == 0, got {tuple(a.shape)}")
+    m, k = a.shape
+    g = a.reshape(m, k // 4, 4)
+    # a stable descending sort of |a| keeps the lower position first among equals
+    pos = g.abs().float().sort(dim=-1, descending=True, stable=True).indices[..., :2].sort(dim=-1).values
+    vals = torch.gather(g, -1, pos).reshape(m, k // 2).to(torch.bfloat16)
+    nib = (pos[..., 0] | (pos[..., 1] << 2)).reshape(m, k // 8, 2)
+    return vals.contiguous(), (nib[..., 0] | (nib[..., 1] << 4)).to(torch.uint8).contiguous()
+
+
 def f8_fill(buf, seed: int, kind: str = "e4m3"):
     """The FP8 / FP4 readiness operand fill into ``buf`` (byte size % 16): finite hashed ``e4m3`` / ``e5m2``
     bytes with |x| in [0.5, 1), E8M0 block ``scale`` bytes in [124, 131], ``e2m1`` / ``i8``: any byte (two
-    finite FP4 codes, or one int8, -128 included), or ``f64``: finite doubles with a hashed sign, |x| in
-    [0.5, 1) and all 52 mantissa bits hashed."""
+    finite FP4 codes, or one int8, -128 included), ``f64``: finite doubles with a hashed sign, |x| in
+    [0.5, 1) and all 52 mantissa bits hashed, or ``meta24``: 2:4 metadata, every nibble one of the six legal
+    codes 4, 8, 12, 9, 13, 14."""
     if kind not in F8_FILL_KINDS:
         raise ProbeError(f"unknown f8 fill {kind!r}: {sorted(F8_FILL_KINDS)}")
     _check(lib().amdprobe_f8_fill(buf.data_ptr(), buf.numel() * buf.element_size(), seed & 0xFFFFFFFF,
@@ -393,7 +488,9 @@ def readiness_f8(device: int = 0, seed: int = 0, mode: str = "fp8", inject: int 
     block scales on the f4 GEMM; ``int8`` = any-byte int8 operands on the i8 GEMM, whose check is exact: a healthy
     device returns 0.0;
     ``fp64`` = hashed doubles on the f64 GEMM at 256 x 256 x 128, checked in fp64: judge it by
-    ``gpu_health.MAX_GEMM_F64_REL_ERR``), the dense
+    ``gpu_health.MAX_GEMM_F64_REL_ERR``; ``sparse24`` = hashed compressed bf16 values, hashed legal 2:4 metadata
+    and a dense hashed bt on the sparse GEMM at ``READINESS_SP_SHAPE``, checked by the dense bf16 check against
+    the VALU expansion of the compressed A), the dense
     VALU check of every element, one read-back on a private stream. Returns ``gemm_rel_err``. ``inject`` = 1
     loses a product tile, 3 skips the GEMM (tests). The GIL is released for the duration (ctypes)."""
     if mode not in READINESS_F8_MODES:

@@ -7,6 +7,7 @@
 #include "f4_kernels.hip"
 #include "i8_kernels.hip"
 #include "f64_kernels.hip"
+#include "sp_kernels.hip"
 
 #include <climits>
 #include <cmath>
@@ -138,11 +139,23 @@ static int launch_fill_f64(void* p, size_t bytes, unsigned seed, void* res, void
   return (int)hipGetLastError();
 }
 
+// The 2:4 metadata fill (hashed_fill_meta24_kernel), with launch_fill's contract.
+static int launch_fill_meta24(void* p, size_t bytes, unsigned seed, void* res, void* stream) {
+  if (bytes == 0 || bytes % 16) return ERR_SHAPE;
+  if (!aligned16(p) || !aligned16(res)) return ERR_ALIGN;
+  const size_t n16 = bytes / 16;
+  const int blocks = (int)((n16 + 255) / 256 < 1024 ? (n16 + 255) / 256 : 1024);
+  hipLaunchKernelGGL(hashed_fill_meta24_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (uint4*)p, n16,
+                     (uint32_t)seed, (ReadinessResult*)res);
+  return (int)hipGetLastError();
+}
+
 // The FP8 / FP4 readiness fill: kind 0 = E4M3 bytes, 1 = E5M2 bytes, 2 = E8M0 block scales, 3 = packed
-// E2M1 nibbles (see hashed_fill_kernel), 5 = fp64 (hashed_fill_f64_kernel). `res` may be null; otherwise
-// see launch_fill.
+// E2M1 nibbles (see hashed_fill_kernel), 5 = fp64 (hashed_fill_f64_kernel), 6 = legal 2:4 metadata nibbles
+// (hashed_fill_meta24_kernel). `res` may be null; otherwise see launch_fill.
 AMDPROBE_EXPORT int amdprobe_f8_fill(void* p, size_t bytes, unsigned seed, int kind, float* res, void* stream) {
   if (kind == FILL_F64) return launch_fill_f64(p, bytes, seed, res, stream);
+  if (kind == FILL_META24) return launch_fill_meta24(p, bytes, seed, res, stream);
   return kind > FILL_E2M1 ? (int)ERR_SHAPE : launch_fill(p, bytes, seed, kind, 0, res, stream);
 }
 
@@ -254,10 +267,34 @@ AMDPROBE_EXPORT int amdprobe_gemm_f64_check(const void* A, const void* Bt, const
 }
 
 // ---------------------------------------------------------------------------------------
+// 2:4 sparse bf16 (sp_kernels.hip). vals: bf16 [M][K/2], meta: uint8 [M][K/8], Bt: bf16 [N][K]; C: fp32.
+// M % 256, N % 128, K % 128. The metadata nibbles are not validated (see sp24_expand_kernel).
+// ---------------------------------------------------------------------------------------
+AMDPROBE_EXPORT int amdprobe_gemm_sp_bf16_nt(const void* vals, const void* meta, const void* Bt, float* C, int M,
+                                             int N, int K, void* stream) {
+  if (const int rc = check_args(M, N, K, sp::BN, sp::BK, INT_MAX, nullptr, nullptr, {vals, meta, Bt, C})) return rc;
+  if (M % sp::BM) return ERR_SHAPE;
+  hipLaunchKernelGGL(gemm_sp_bf16_nt_kernel, dim3((M / sp::BM) * (N / sp::BN)), dim3(sp::THREADS), 0,
+                     (hipStream_t)stream, (const __bf16*)vals, (const uint8_t*)meta, (const __bf16*)Bt, C, M, N, K);
+  return (int)hipGetLastError();
+}
+
+// The dense bf16 A[M][K] of a compressed (vals, meta) pair. K % 8 == 0.
+AMDPROBE_EXPORT int amdprobe_sp24_expand(const void* vals, const void* meta, void* A, int M, int K, void* stream) {
+  if (M <= 0 || K <= 0 || K % 8) return ERR_SHAPE;
+  if (!aligned16(vals) || !aligned16(A)) return ERR_ALIGN;
+  const size_t n = (size_t)M * (K / 8);
+  const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+  hipLaunchKernelGGL(sp24_expand_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint2*)vals,
+                     (const uint8_t*)meta, (uint4*)A, n);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
 // The readiness checks: the whole check of one device in one call (see probe_kernels.hip). Buffers, a
 // non-blocking stream and a pinned result slot are created on first use per device and reused; calls
 // for one device serialize on its context, and the bf16 and f8 / f4 paths have contexts of their own
-// and so has fp64
+// and so have fp64 and sparse24
 // (they neither wait for each other nor allocate each other's buffers). The calling thread's current
 // device is restored. Returns 0 or a HIP error / negative shape code.
 //
@@ -282,7 +319,8 @@ struct ProbeCtx {
   ReadinessResult* host = nullptr;  // pinned
   uint32_t calls = 0;               // mixed into the seed: no two calls share operands or pattern
 };
-ProbeCtx g_readiness[MAX_DEVICES], g_readiness_f8[MAX_DEVICES], g_readiness_f64[MAX_DEVICES];
+ProbeCtx g_readiness[MAX_DEVICES], g_readiness_f8[MAX_DEVICES], g_readiness_f64[MAX_DEVICES],
+    g_readiness_sp[MAX_DEVICES];
 constexpr size_t BF16_BYTES[PROBE_BUFS] = {size_t(RM + RN) * RK * sizeof(__bf16), C_BYTES, PATTERN_BYTES};
 constexpr size_t F8_BYTES[PROBE_BUFS] = {size_t(RM + RN) * RK, C_BYTES, size_t(RM + RN) * (RK / 32)};
 // fp64: K = 128 is 8 K-tiles of 16, so the three-stage ring of gemm_f64_nt_kernel reaches its steady state
@@ -290,6 +328,14 @@ constexpr size_t F8_BYTES[PROBE_BUFS] = {size_t(RM + RN) * RK, C_BYTES, size_t(R
 // used; the slot gets 16 bytes.
 constexpr int RK64 = 128;
 constexpr size_t F64_BYTES[PROBE_BUFS] = {size_t(RM + RN) * RK64 * sizeof(double), size_t(RM) * RN * sizeof(double), 16};
+// sparse24: K = 512 is SP_RING + 2 = 4 K-tiles of 128 = 8 half-stages of gemm_sp_bf16_nt_kernel's ring of four:
+// every ring slot gets a second occupant, the counted vmcnt(9) waits of the steady state run (they need a K-tile
+// T + 2) and so do the shorter ones of the last two K-tiles. It is the smallest K that does all three, and below
+// the dense check's CHECK_MAX_K. BUF_AB holds the expanded A, then Bt, then vals (Bt and vals are filled as
+// one run of hashed bf16); the aux buffer is the metadata. The 256 x 256 product is two 256 x 128 workgroups.
+constexpr int RKSP = 512;
+constexpr size_t SP_A_BYTES = size_t(RM) * RKSP * sizeof(__bf16), SP_BT_BYTES = size_t(RN) * RKSP * sizeof(__bf16);
+constexpr size_t SP_BYTES[PROBE_BUFS] = {SP_A_BYTES + SP_BT_BYTES + SP_A_BYTES / 2, C_BYTES, size_t(RM) * (RKSP / 8)};
 
 struct DeviceGuard {
   int prev = -1;
@@ -395,8 +441,26 @@ AMDPROBE_EXPORT int amdprobe_readiness(int device, unsigned seed, int inject, do
 // launch (both must fail). There is no HBM pattern here: amdprobe_readiness does that.
 // Mode 5 = fp64 runs on a context and buffers of its own (8-byte operands and product do not fit F8_BYTES):
 // hashed doubles, C poisoned with 0xFF bytes (a double NaN), the f64 GEMM, its fp64 check, one read-back.
+// Mode 6 = sparse24, also on a context of its own: hashed bf16 vals and Bt, hashed legal metadata, the VALU
+// expansion to a dense A, C poisoned, the sparse GEMM, and the dense bf16 check of C against expanded A x Bt^T.
 AMDPROBE_EXPORT int amdprobe_readiness_f8(int device, unsigned seed, int mode, int inject, double* rel_err) {
-  if (mode < 0 || mode > 5) return ERR_SHAPE;
+  if (mode < 0 || mode > 6) return ERR_SHAPE;
+  if (mode == 6)
+    return run_probe(g_readiness_sp, SP_BYTES, device, seed, rel_err, nullptr, [&](ProbeCtx& ctx, uint32_t call_seed) {
+      hipStream_t s = ctx.stream;
+      char* A = (char*)ctx.buf[BUF_AB];
+      char* Bt = A + SP_A_BYTES;
+      char* vals = Bt + SP_BT_BYTES;
+      void* meta = ctx.buf[BUF_AUX];
+      float* C = (float*)ctx.buf[BUF_C];
+      PROBE_TRY(launch_fill(Bt, SP_BT_BYTES + SP_A_BYTES / 2, call_seed, FILL_BF16, 0, ctx.res, s));
+      PROBE_TRY(launch_fill_meta24(meta, SP_BYTES[BUF_AUX], call_seed ^ 0x5CA1E5u, nullptr, s));
+      PROBE_TRY(amdprobe_sp24_expand(vals, meta, A, RM, RKSP, s));
+      PROBE_TRY(hipMemsetAsync(C, 0xFF, C_BYTES, s));  // NaN until the GEMM writes
+      if (inject != 3) PROBE_TRY(amdprobe_gemm_sp_bf16_nt(vals, meta, Bt, C, RM, RN, RKSP, s));
+      PROBE_TRY(amdprobe_gemm_check(A, Bt, C, RM, RN, RKSP, inject == 1 ? 1 : 0, &ctx.res->diff2, s));
+      return 0;
+    });
   if (mode == 5)
     return run_probe(g_readiness_f64, F64_BYTES, device, seed, rel_err, nullptr, [&](ProbeCtx& ctx, uint32_t call_seed) {
       hipStream_t s = ctx.stream;

@@ -17,6 +17,10 @@ Runs the HIP probe kernels on one device and decides healthy / unhealthy:
   path HPC payloads run on: the f64 GEMM on hashed doubles against an fp64 VALU reference, the difference
   taken in fp64. Its bound is ``MAX_GEMM_F64_REL_ERR`` = 1e-10, not 1e-3: a product silently computed at
   single precision (2^-24) must fail;
+* **2:4 sparse MFMA numerics** (opt-in, ``sparse24``) -- ``v_smfmac_f32_16x16x64_bf16``, whose per-lane index
+  register drives a 2-of-4 operand mux that no dense instruction uses: the sparse GEMM on a compressed hashed A
+  with hashed legal metadata, against the dense bf16 VALU check of the expanded A. The sparse product has the
+  terms of the dense one, so the bound is the shared < 1e-3; a wrong index gives an O(1) error;
 * **MFMA rate** -- register-resident ``v_mfma_f32_32x32x16_bf16`` loop (TFLOP/s);
 * **HBM** -- 16-B/lane streaming copy of a buffer larger than the 256 MiB Infinity Cache
   (read+write GB/s) and an address-hashed write/verify pattern (bad words must be 0).
@@ -42,7 +46,7 @@ MAX_GEMM_REL_ERR = 1e-3
 # the shared 1e-3 would pass. 1e-10 is near the geometric middle of the two (1.4e-10).
 MAX_GEMM_F64_REL_ERR = 1e-10
 # bf16 is always checked; the rest are opt-in
-MATRIX_MODES = ("bf16", "fp8", "bf8", "mxfp8", "mxfp4", "int8", "fp64")
+MATRIX_MODES = ("bf16", "fp8", "bf8", "mxfp8", "mxfp4", "int8", "fp64", "sparse24")
 
 
 def _max_rel_err(mode: str) -> float:
@@ -61,7 +65,7 @@ def readiness_probe(device: int = 0, matrix=("bf16",)) -> dict:
     native call (``ops.readiness``): hashed bf16 operands, the MFMA GEMM, a dense fp32 check of
     every product element and the 64 MiB pattern test on a private stream with a single read-back. It sits on the deploy and
     recovery critical path of every GPU pod, and the GIL is released while it runs. Each of ``fp8``, ``bf8``,
-    ``mxfp8``, ``mxfp4``, ``int8``, ``fp64`` in ``matrix`` adds one ``ops.readiness_f8`` call and a ``gemm_<mode>_rel_err`` field."""
+    ``mxfp8``, ``mxfp4``, ``int8``, ``fp64``, ``sparse24`` in ``matrix`` adds one ``ops.readiness_f8`` call and a ``gemm_<mode>_rel_err`` field."""
     from dcos_commons_amd import ops
 
     t0 = time.perf_counter()
@@ -147,6 +151,23 @@ def run_probe(device: int = 0, quick: bool = True, matrix=("bf16",)) -> dict:
             report["gemm_fp64_tflops"] = round(2.0 * s * s * s * reps / (e0.elapsed_time(e1) / 1e3) / 1e12, 1)
             del ab64, out64
             continue
+        if mode == "sparse24":
+            # gemm_sparse24_tflops counts 2 * s^3, the flops of the dense product of the same square shape
+            # (dense-equivalent: the kernel multiplies half of them)
+            vb = torch.empty((s + s // 2, s), dtype=torch.bfloat16, device=dev)
+            ops.readiness_fill(vb, seed=1234 + device)
+            va, vbt = vb[s:].reshape(s, s // 2), vb[:s]
+            vm = torch.empty((s, s // 8), dtype=torch.uint8, device=dev)
+            ops.f8_fill(vm, seed=1234 + device, kind="meta24")
+            ops.gemm_sp_bf16_nt(va, vm, vbt, out=out)
+            e0.record()
+            for _ in range(reps):
+                ops.gemm_sp_bf16_nt(va, vm, vbt, out=out)
+            e1.record()
+            e1.synchronize()
+            report["gemm_sparse24_tflops"] = round(2.0 * s * s * s * reps / (e0.elapsed_time(e1) / 1e3) / 1e12, 1)
+            del vb, va, vbt, vm
+            continue
         dt = torch.uint8 if mode == "mxfp4" else torch.float8_e5m2 if mode == "bf8" else torch.float8_e4m3fn
         ab8 = torch.empty((2 * s, s // 2 if mode == "mxfp4" else s), dtype=torch.uint8, device=dev)
         ops.f8_fill(ab8, seed=1234 + device, kind={"bf8": "e5m2", "mxfp4": "e2m1"}.get(mode, "e4m3"))
@@ -206,7 +227,7 @@ def main(argv=None) -> int:
     ap.add_argument("--full", action="store_true", help="larger shapes (slower, more precise)")
     ap.add_argument("--readiness", action="store_true", help="fast numerics + memory check only")
     ap.add_argument("--matrix", default="bf16", help="comma-separated matrix data paths to check: bf16 (always), "
-                    "fp8, bf8, mxfp8, mxfp4, int8, fp64")
+                    "fp8, bf8, mxfp8, mxfp4, int8, fp64, sparse24")
     ap.add_argument("--json", action="store_true")
     args = ap.parse_args(argv)
     matrix = tuple(m for m in args.matrix.split(",") if m)
