@@ -1,6 +1,6 @@
 """MI355X device ops: HIP probe kernels behind a torch-tensor API.
 
-The kernels live in six files under ``csrc/``:
+The kernels live in seven files under ``csrc/``:
 
 * ``probe_kernels.hip``: MFMA bf16 GEMM, MFMA issue-rate loop, HBM streaming copy, HBM pattern test,
   the hashed operand fill and the shared parts of the dense VALU check;
@@ -11,7 +11,9 @@ The kernels live in six files under ``csrc/``:
   subtracts in fp64, and the hashed fp64 operand fill;
 * ``sp_kernels.hip``: 2:4 sparse bf16 MFMA GEMM (``v_smfmac_f32_16x16x64_bf16``) on a compressed A, the VALU
   expansion of a compressed A to dense (the dense bf16 check then serves as its reference) and the hashed
-  metadata fill.
+  metadata fill;
+* ``f32_kernels.hip``: FP32 MFMA GEMM (``v_mfma_f32_32x32x2_f32``, 4-byte operands) and its check against an
+  fp32 VALU reference; its operands come from the shared hashed fill with an fp32 mask pair.
 
 They are compiled for gfx950 into the in-tree ``_amdprobe.so`` (``python -m dcos_commons_amd.ops.build``)
 and back the GPU readiness/health check that gates pods which request ``gpus``
@@ -72,6 +74,8 @@ def _bind(lib: ctypes.CDLL) -> None:
             ("gemm_f64_check", i, [vp, vp, vp, i, i, i, i, vp, vp]),
             ("gemm_sp_bf16_nt", i, [vp, vp, vp, vp, i, i, i, vp]),
             ("sp24_expand", i, [vp, vp, vp, i, i, vp]),
+            ("gemm_f32_nt", i, [vp, vp, vp, i, i, i, vp]),
+            ("gemm_f32_check", i, [vp, vp, vp, i, i, i, i, vp, vp]),
             ("readiness_f8", i, [i, u, i, i, pd])):
         fn = getattr(lib, "amdprobe_" + name)
         fn.restype = restype
@@ -109,8 +113,10 @@ def _check(rc: int, what: str) -> None:
 
 F8_TILE = 128                       # M, N and K granule of gemm_f8_nt
 F8_BLOCK = 32                       # K elements per E8M0 block scale
-F8_FILL_KINDS = {"e4m3": 0, "e5m2": 1, "scale": 2, "e2m1": 3, "i8": 3, "f64": 5, "meta24": 6}   # i8: the any-byte fill
-READINESS_F8_MODES = {"fp8": 0, "bf8": 1, "mxfp8": 2, "mxfp4": 3, "int8": 4, "fp64": 5, "sparse24": 6}
+F8_FILL_KINDS = {"e4m3": 0, "e5m2": 1, "scale": 2, "e2m1": 3, "i8": 3, "f64": 5, "meta24": 6,
+                 "f32": 7}          # i8: the any-byte fill
+READINESS_F8_MODES = {"fp8": 0, "bf8": 1, "mxfp8": 2, "mxfp4": 3, "int8": 4, "fp64": 5, "sparse24": 6,
+                      "fp32": 7}
 F4_TILE_MN = 256                    # M and N granule of gemm_f4_nt
 F4_TILE_K = 256                     # K granule (elements) of gemm_f4_nt
 I8_TILE_MN = 256                    # M and N granule of gemm_i8_nt
@@ -126,9 +132,15 @@ SP_TILE_N = 128                     # its N granule
 SP_TILE_K = 128                     # its K granule, in dense K elements (64 compressed values, 16 metadata bytes)
 SP_RING = 2                         # K-tiles in its LDS ring (held as four half-tile stages)
 READINESS_SP_SHAPE = (256, 256, 512)    # M, N, dense K of the sparse24 readiness GEMM (csrc/probe_api.hip)
+F32_TILE_M = 256                    # M granule of gemm_f32_nt
+F32_TILE_N = 256                    # its N granule
+F32_TILE_K = 32                     # its K granule (one 128-byte row of floats)
+F32_RING = 2                        # K-tiles in its LDS ring
+READINESS_F32_SHAPE = (256, 256, 128)   # M, N, K of the fp32 readiness GEMM (csrc/probe_api.hip)
 _CHECK_TILE = 16                    # M and N granule of the dense checks
 _CHECK_MAX_K = 1024                 # their largest K (one tile's operand rows sit in LDS)
 _CHECK_F64_MAX_K = 256              # the fp64 check's: its rows are 8 * K bytes
+_CHECK_F32_MAX_K = 512              # the fp32 check's: its rows are 4 * K bytes
 
 
 def _operands(what: str, kind: str, a, bt, granule: int, k_granule: int, k_max=None, a_scale=None, bt_scale=None,
@@ -136,7 +148,8 @@ def _operands(what: str, kind: str, a, bt, granule: int, k_granule: int, k_max=N
     """Validates the operands of a GEMM or check wrapper before native code sees their pointers; returns
     ``(a, bt, a_scale, bt_scale, res, m, n, k, fmt)`` with contiguous tensors. ``kind`` is ``bf16``, ``fp8``
     (``fmt`` = the two format codes of the native call, else ``()``), ``int8`` (the product is int32, not
-    float32), ``fp64`` (float64 operands and product; ``granule`` may be an ``(M, N)`` pair) or ``fp4`` (packed: K is twice the row length; the operands come back as uint8). ``res`` is the product: ``c`` made contiguous when the caller
+    float32), ``fp64`` (float64 operands and product; ``granule`` may be an ``(M, N)`` pair), ``fp32`` (float32 operands and
+    product) or ``fp4`` (packed: K is twice the row length; the operands come back as uint8). ``res`` is the product: ``c`` made contiguous when the caller
     has one to check, else ``out``, allocated when ``None``. Shape, granule, dtype and paired-scale errors
     are reported first; then every tensor must be on the operands' one GPU, and the product a float32
     ``(m, n)``, a caller's ``out`` contiguous as well (the kernel writes through its pointer)."""
@@ -156,6 +169,8 @@ def _operands(what: str, kind: str, a, bt, granule: int, k_granule: int, k_max=N
         ok, expects = a.dtype == bt.dtype == torch.int8, "int8"
     elif kind == "fp64":
         ok, expects = a.dtype == bt.dtype == torch.float64, "float64"
+    elif kind == "fp32":
+        ok, expects = a.dtype == bt.dtype == torch.float32, "float32"
     else:
         packed = (torch.uint8, getattr(torch, "float4_e2m1fn_x2", torch.uint8))
         ok, expects = a.dtype in packed and bt.dtype in packed, "packed E2M1 (uint8 or float4_e2m1fn_x2)"
@@ -386,6 +401,26 @@ def gemm_f64_check(a, bt, c, inject: int = 0):
                       c.data_ptr(), m, n, k, inject)
 
 
+def gemm_f32_nt(a, bt, out=None):
+    """``a[M,K] @ bt[N,K]^T`` in fp32 on the FP32 MFMA kernel (``v_mfma_f32_32x32x2_f32``); ``a`` / ``bt`` are
+    ``float32``, M, N % 256 == 0, K % 32 == 0. Every product and sum is the instruction's; the result differs
+    from a sequential sum only in summation order."""
+    a, bt, _, _, out, m, n, k, _ = _operands("gemm_f32_nt", "fp32", a, bt, (F32_TILE_M, F32_TILE_N), F32_TILE_K,
+                                             out=out)
+    _check(lib().amdprobe_gemm_f32_nt(a.data_ptr(), bt.data_ptr(), out.data_ptr(), m, n, k, _stream(a.device)),
+           "gemm_f32_nt")
+    return out
+
+
+def gemm_f32_check(a, bt, c, inject: int = 0):
+    """Dense check of an FP32 product ``c`` (float32) on the GPU, every element against an fp32 VALU reference
+    (``v_fma_f32``) that never touches the matrix pipe: returns ``(sum((c - ref)^2), sum(ref^2))``.
+    M, N % 16 == 0, K % 8 == 0, K <= 512."""
+    a, bt, _, _, c, m, n, k, _ = _operands("gemm_f32_check", "fp32", a, bt, _CHECK_TILE, 8, _CHECK_F32_MAX_K, c=c)
+    return _run_check("gemm_f32_check", lib().amdprobe_gemm_f32_check, a.device, a.data_ptr(), bt.data_ptr(),
+                      c.data_ptr(), m, n, k, inject)
+
+
 def _sp_operands(what: str, a_vals, a_meta, others=()):
     """Validates a compressed 2:4 pair before native code sees a pointer; returns ``(a_vals, a_meta, m, k)``,
     contiguous, ``k`` the dense K. Dtypes and shapes first; then ``a_vals``, ``a_meta`` and every ``(name,
@@ -474,8 +509,9 @@ def f8_fill(buf, seed: int, kind: str = "e4m3"):
     """The FP8 / FP4 readiness operand fill into ``buf`` (byte size % 16): finite hashed ``e4m3`` / ``e5m2``
     bytes with |x| in [0.5, 1), E8M0 block ``scale`` bytes in [124, 131], ``e2m1`` / ``i8``: any byte (two
     finite FP4 codes, or one int8, -128 included), ``f64``: finite doubles with a hashed sign, |x| in
-    [0.5, 1) and all 52 mantissa bits hashed, or ``meta24``: 2:4 metadata, every nibble one of the six legal
-    codes 4, 8, 12, 9, 13, 14."""
+    [0.5, 1) and all 52 mantissa bits hashed, ``meta24``: 2:4 metadata, every nibble one of the six legal
+    codes 4, 8, 12, 9, 13, 14, or ``f32``: finite floats with a hashed sign, |x| in [0.5, 1) and all 23 mantissa
+    bits hashed."""
     if kind not in F8_FILL_KINDS:
         raise ProbeError(f"unknown f8 fill {kind!r}: {sorted(F8_FILL_KINDS)}")
     _check(lib().amdprobe_f8_fill(buf.data_ptr(), buf.numel() * buf.element_size(), seed & 0xFFFFFFFF,
@@ -490,7 +526,8 @@ def readiness_f8(device: int = 0, seed: int = 0, mode: str = "fp8", inject: int 
     ``fp64`` = hashed doubles on the f64 GEMM at 256 x 256 x 128, checked in fp64: judge it by
     ``gpu_health.MAX_GEMM_F64_REL_ERR``; ``sparse24`` = hashed compressed bf16 values, hashed legal 2:4 metadata
     and a dense hashed bt on the sparse GEMM at ``READINESS_SP_SHAPE``, checked by the dense bf16 check against
-    the VALU expansion of the compressed A), the dense
+    the VALU expansion of the compressed A; ``fp32`` = hashed floats on the f32 GEMM at ``READINESS_F32_SHAPE``,
+    checked against an fp32 VALU reference: judge it by ``gpu_health.MAX_GEMM_F32_REL_ERR``), the dense
     VALU check of every element, one read-back on a private stream. Returns ``gemm_rel_err``. ``inject`` = 1
     loses a product tile, 3 skips the GEMM (tests). The GIL is released for the duration (ctypes)."""
     if mode not in READINESS_F8_MODES:

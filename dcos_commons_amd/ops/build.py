@@ -27,7 +27,7 @@ BUILD = os.path.join(NATIVE, "build")
 BUILD_SANITIZE = os.path.join(NATIVE, "build-sanitize")  # ASan/UBSan host tools (tests only)
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0] or "gfx950"
 KERNEL_SRCS = ("probe_kernels.hip", "f8_kernels.hip", "f4_kernels.hip", "i8_kernels.hip",
-               "f64_kernels.hip", "sp_kernels.hip")  # #included by probe_api.hip
+               "f64_kernels.hip", "sp_kernels.hip", "f32_kernels.hip")  # #included by probe_api.hip
 # no packed-fp32 VALU forms (v_pk_fma_f32 and kin) in the kernels' scalar fp32 math
 DEVICE_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 

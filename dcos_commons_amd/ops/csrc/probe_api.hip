@@ -8,6 +8,7 @@
 #include "i8_kernels.hip"
 #include "f64_kernels.hip"
 #include "sp_kernels.hip"
+#include "f32_kernels.hip"
 
 #include <climits>
 #include <cmath>
@@ -113,14 +114,25 @@ AMDPROBE_EXPORT int amdprobe_gemm_check(const void* A, const void* Bt, const flo
 // The hashed operand fill (tests compare it with a host model of the hash). `blocks` 0 sizes the
 // grid to the buffer, at most 1024 workgroups. `res`, when not null, is a 32-byte ReadinessResult
 // slot and is zeroed.
-static int launch_fill(void* p, size_t bytes, unsigned seed, int kind, int blocks, void* res, void* stream) {
-  if (bytes == 0 || bytes % 16 || kind < 0 || kind >= FILL_KINDS) return ERR_SHAPE;
+static int launch_fill_pair(void* p, size_t bytes, unsigned seed, uint32_t and4, uint32_t add4, int blocks, void* res,
+                            void* stream) {
+  if (bytes == 0 || bytes % 16) return ERR_SHAPE;
   if (!aligned16(p) || !aligned16(res)) return ERR_ALIGN;
   const size_t n16 = bytes / 16;
   if (blocks == 0) blocks = (int)((n16 + 255) / 256 < 1024 ? (n16 + 255) / 256 : 1024);
   hipLaunchKernelGGL(hashed_fill_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (uint4*)p, n16,
-                     (uint32_t)seed, FILL_AND4[kind], FILL_ADD4[kind], (ReadinessResult*)res);
+                     (uint32_t)seed, and4, add4, (ReadinessResult*)res);
   return (int)hipGetLastError();
+}
+
+static int launch_fill(void* p, size_t bytes, unsigned seed, int kind, int blocks, void* res, void* stream) {
+  if (kind < 0 || kind >= FILL_KINDS) return ERR_SHAPE;
+  return launch_fill_pair(p, bytes, seed, FILL_AND4[kind], FILL_ADD4[kind], blocks, res, stream);
+}
+
+// The fp32 fill: hashed_fill_kernel with the dword pair of f32_kernels.hip, with launch_fill's contract.
+static int launch_fill_f32(void* p, size_t bytes, unsigned seed, void* res, void* stream) {
+  return launch_fill_pair(p, bytes, seed, FILL_F32_AND, FILL_F32_ADD, 0, res, stream);
 }
 
 // The bf16 readiness fill: `ab` gets `ab_bytes` of hashed bf16 and `res` (32 bytes) is zeroed.
@@ -152,10 +164,12 @@ static int launch_fill_meta24(void* p, size_t bytes, unsigned seed, void* res, v
 
 // The FP8 / FP4 readiness fill: kind 0 = E4M3 bytes, 1 = E5M2 bytes, 2 = E8M0 block scales, 3 = packed
 // E2M1 nibbles (see hashed_fill_kernel), 5 = fp64 (hashed_fill_f64_kernel), 6 = legal 2:4 metadata nibbles
-// (hashed_fill_meta24_kernel). `res` may be null; otherwise see launch_fill.
+// (hashed_fill_meta24_kernel), 7 = fp32 (hashed_fill_kernel, sign and 23 mantissa bits hashed, exponent 126). `res`
+// may be null; otherwise see launch_fill.
 AMDPROBE_EXPORT int amdprobe_f8_fill(void* p, size_t bytes, unsigned seed, int kind, float* res, void* stream) {
   if (kind == FILL_F64) return launch_fill_f64(p, bytes, seed, res, stream);
   if (kind == FILL_META24) return launch_fill_meta24(p, bytes, seed, res, stream);
+  if (kind == FILL_F32) return launch_fill_f32(p, bytes, seed, res, stream);
   return kind > FILL_E2M1 ? (int)ERR_SHAPE : launch_fill(p, bytes, seed, kind, 0, res, stream);
 }
 
@@ -291,6 +305,25 @@ AMDPROBE_EXPORT int amdprobe_sp24_expand(const void* vals, const void* meta, voi
 }
 
 // ---------------------------------------------------------------------------------------
+// FP32 (f32_kernels.hip). A, Bt: floats, 4 * K bytes per row; C: fp32. M, N % 256, K % 32.
+// ---------------------------------------------------------------------------------------
+AMDPROBE_EXPORT int amdprobe_gemm_f32_nt(const void* A, const void* Bt, float* C, int M, int N, int K, void* stream) {
+  static_assert(f32::BM == f32::BN, "one M, N granule");
+  if (const int rc = check_args(M, N, K, f32::BM, f32::BK, INT_MAX, nullptr, nullptr, {A, Bt, C})) return rc;
+  hipLaunchKernelGGL(gemm_f32_nt_kernel, dim3((M / f32::BM) * (N / f32::BN)), dim3(f32::THREADS), 0,
+                     (hipStream_t)stream, (const float*)A, (const float*)Bt, C, M, N, K);
+  return (int)hipGetLastError();
+}
+
+AMDPROBE_EXPORT int amdprobe_gemm_f32_check(const void* A, const void* Bt, const float* C, int M, int N, int K,
+                                            int inject, float* out2, void* stream) {
+  if (const int rc = check_args(M, N, K, CHECK_TILE, 8, f32::CHECK_MAX_K, nullptr, nullptr, {A, Bt})) return rc;
+  hipLaunchKernelGGL(gemm_f32_check_kernel, dim3((M / CHECK_TILE) * (N / CHECK_TILE)), dim3(CHECK_THREADS), 0,
+                     (hipStream_t)stream, (const float*)A, (const float*)Bt, C, M, N, K, inject, out2);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
 // The readiness checks: the whole check of one device in one call (see probe_kernels.hip). Buffers, a
 // non-blocking stream and a pinned result slot are created on first use per device and reused; calls
 // for one device serialize on its context, and the bf16 and f8 / f4 paths have contexts of their own
@@ -334,6 +367,11 @@ constexpr size_t F64_BYTES[PROBE_BUFS] = {size_t(RM + RN) * RK64 * sizeof(double
 // the dense check's CHECK_MAX_K. BUF_AB holds the expanded A, then Bt, then vals (Bt and vals are filled as
 // one run of hashed bf16); the aux buffer is the metadata. The 256 x 256 product is two 256 x 128 workgroups.
 constexpr int RKSP = 512;
+// fp32: K = (f32::RING + 2) * f32::BK = 128 is 4 K-tiles on gemm_f32_nt_kernel's ring of two: every ring slot gets
+// a second occupant, and the prologue's counted wait, the loop's barrier with and without a stage after it and the
+// barrier-free last tile all run. The product is one 256 x 256 workgroup. Operands and product are exactly the
+// sizes of the f8 context's buffers, so the mode runs there, as int8 does.
+constexpr int RK32 = (f32::RING + 2) * f32::BK;
 constexpr size_t SP_A_BYTES = size_t(RM) * RKSP * sizeof(__bf16), SP_BT_BYTES = size_t(RN) * RKSP * sizeof(__bf16);
 constexpr size_t SP_BYTES[PROBE_BUFS] = {SP_A_BYTES + SP_BT_BYTES + SP_A_BYTES / 2, C_BYTES, size_t(RM) * (RKSP / 8)};
 
@@ -443,8 +481,26 @@ AMDPROBE_EXPORT int amdprobe_readiness(int device, unsigned seed, int inject, do
 // hashed doubles, C poisoned with 0xFF bytes (a double NaN), the f64 GEMM, its fp64 check, one read-back.
 // Mode 6 = sparse24, also on a context of its own: hashed bf16 vals and Bt, hashed legal metadata, the VALU
 // expansion to a dense A, C poisoned, the sparse GEMM, and the dense bf16 check of C against expanded A x Bt^T.
+// Mode 7 = fp32, on the f8 context (its operands and product have the sizes of that context's buffers): hashed
+// floats, C poisoned, the f32 GEMM at 256 x 256 x 128, its fp32 VALU check, one read-back.
 AMDPROBE_EXPORT int amdprobe_readiness_f8(int device, unsigned seed, int mode, int inject, double* rel_err) {
-  if (mode < 0 || mode > 6) return ERR_SHAPE;
+  if (mode < 0 || mode > 7) return ERR_SHAPE;
+  if (mode == 7) {
+    static_assert(size_t(RM + RN) * RK32 * sizeof(float) == F8_BYTES[BUF_AB] && RM % f32::BM == 0 &&
+                      RN % f32::BN == 0 && RK32 <= f32::CHECK_MAX_K,
+                  "the fp32 mode runs on the f8 context's buffers");
+    return run_probe(g_readiness_f8, F8_BYTES, device, seed, rel_err, nullptr, [&](ProbeCtx& ctx, uint32_t call_seed) {
+      hipStream_t s = ctx.stream;
+      const float* A = (const float*)ctx.buf[BUF_AB];
+      const float* Bt = A + size_t(RM) * RK32;
+      float* C = (float*)ctx.buf[BUF_C];
+      PROBE_TRY(launch_fill_f32(ctx.buf[BUF_AB], F8_BYTES[BUF_AB], call_seed, ctx.res, s));
+      PROBE_TRY(hipMemsetAsync(C, 0xFF, C_BYTES, s));  // NaN until the GEMM writes
+      if (inject != 3) PROBE_TRY(amdprobe_gemm_f32_nt(A, Bt, C, RM, RN, RK32, s));
+      PROBE_TRY(amdprobe_gemm_f32_check(A, Bt, C, RM, RN, RK32, inject == 1 ? 1 : 0, &ctx.res->diff2, s));
+      return 0;
+    });
+  }
   if (mode == 6)
     return run_probe(g_readiness_sp, SP_BYTES, device, seed, rel_err, nullptr, [&](ProbeCtx& ctx, uint32_t call_seed) {
       hipStream_t s = ctx.stream;

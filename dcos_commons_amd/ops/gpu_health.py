@@ -21,6 +21,10 @@ Runs the HIP probe kernels on one device and decides healthy / unhealthy:
   register drives a 2-of-4 operand mux that no dense instruction uses: the sparse GEMM on a compressed hashed A
   with hashed legal metadata, against the dense bf16 VALU check of the expanded A. The sparse product has the
   terms of the dense one, so the bound is the shared < 1e-3; a wrong index gives an O(1) error;
+* **FP32 MFMA numerics** (opt-in, ``fp32``) -- ``v_mfma_f32_32x32x2_f32``, the single-precision multiplier array
+  that every SGEMM lands on: the f32 GEMM on hashed floats against an fp32 VALU reference. Its bound is
+  ``MAX_GEMM_F32_REL_ERR`` = 1e-5, not 1e-3: a product whose operands went through an 11-bit (tf32-like) path
+  (2.6e-4) must fail;
 * **MFMA rate** -- register-resident ``v_mfma_f32_32x32x16_bf16`` loop (TFLOP/s);
 * **HBM** -- 16-B/lane streaming copy of a buffer larger than the 256 MiB Infinity Cache
   (read+write GB/s) and an address-hashed write/verify pattern (bad words must be 0).
@@ -45,12 +49,21 @@ MAX_GEMM_REL_ERR = 1e-3
 # 3e-13 at K = 128. Faulty: a product rounded once through fp32 is off by about 2^-24 = 6e-8 per element, which
 # the shared 1e-3 would pass. 1e-10 is near the geometric middle of the two (1.4e-10).
 MAX_GEMM_F64_REL_ERR = 1e-10
+# The fp32 mode's own bound, for the readiness K of 128 (ops.READINESS_F32_SHAPE). It sits between two levels.
+# Faulty: a product whose operands were rounded to 11 significant bits (a tf32 / xf32-like path) is off by 2.6e-4
+# relative Frobenius on hashed-fill-like values, the same at K = 128, 256 and 512 (computed on the CPU in float64;
+# bf16-rounded operands give 2.1e-3). The shared 1e-3 would pass it. Healthy: the GEMM and the VALU reference are
+# both fp32 sums of 128 terms in different orders; two sequential fp32 sums in different orders differ by about
+# 2.5e-7 (a CPU estimate), and readiness_f8(mode="fp32") on a healthy MI355X measured 2.28e-7 to 2.33e-7 over 24
+# seeds (profiles/gemm_f32.md). The geometric mean of 2.33e-7 and 2.6e-4 is 7.8e-6; 1e-5 is the power of ten
+# nearest to it, 43x above the measured maximum and 26x below the faulty level.
+MAX_GEMM_F32_REL_ERR = 1e-5
 # bf16 is always checked; the rest are opt-in
-MATRIX_MODES = ("bf16", "fp8", "bf8", "mxfp8", "mxfp4", "int8", "fp64", "sparse24")
+MATRIX_MODES = ("bf16", "fp8", "bf8", "mxfp8", "mxfp4", "int8", "fp64", "sparse24", "fp32")
 
 
 def _max_rel_err(mode: str) -> float:
-    return MAX_GEMM_F64_REL_ERR if mode == "fp64" else MAX_GEMM_REL_ERR
+    return {"fp64": MAX_GEMM_F64_REL_ERR, "fp32": MAX_GEMM_F32_REL_ERR}.get(mode, MAX_GEMM_REL_ERR)
 
 
 def _f8_modes(matrix) -> list:
@@ -65,7 +78,7 @@ def readiness_probe(device: int = 0, matrix=("bf16",)) -> dict:
     native call (``ops.readiness``): hashed bf16 operands, the MFMA GEMM, a dense fp32 check of
     every product element and the 64 MiB pattern test on a private stream with a single read-back. It sits on the deploy and
     recovery critical path of every GPU pod, and the GIL is released while it runs. Each of ``fp8``, ``bf8``,
-    ``mxfp8``, ``mxfp4``, ``int8``, ``fp64``, ``sparse24`` in ``matrix`` adds one ``ops.readiness_f8`` call and a ``gemm_<mode>_rel_err`` field."""
+    ``mxfp8``, ``mxfp4``, ``int8``, ``fp64``, ``sparse24``, ``fp32`` in ``matrix`` adds one ``ops.readiness_f8`` call and a ``gemm_<mode>_rel_err`` field."""
     from dcos_commons_amd import ops
 
     t0 = time.perf_counter()
@@ -151,6 +164,18 @@ def run_probe(device: int = 0, quick: bool = True, matrix=("bf16",)) -> dict:
             report["gemm_fp64_tflops"] = round(2.0 * s * s * s * reps / (e0.elapsed_time(e1) / 1e3) / 1e12, 1)
             del ab64, out64
             continue
+        if mode == "fp32":
+            ab32 = torch.empty((2 * s, s), dtype=torch.float32, device=dev)
+            ops.f8_fill(ab32, seed=1234 + device, kind="f32")
+            ops.gemm_f32_nt(ab32[:s], ab32[s:], out=out)
+            e0.record()
+            for _ in range(reps):
+                ops.gemm_f32_nt(ab32[:s], ab32[s:], out=out)
+            e1.record()
+            e1.synchronize()
+            report["gemm_fp32_tflops"] = round(2.0 * s * s * s * reps / (e0.elapsed_time(e1) / 1e3) / 1e12, 1)
+            del ab32
+            continue
         if mode == "sparse24":
             # gemm_sparse24_tflops counts 2 * s^3, the flops of the dense product of the same square shape
             # (dense-equivalent: the kernel multiplies half of them)
@@ -227,7 +252,7 @@ def main(argv=None) -> int:
     ap.add_argument("--full", action="store_true", help="larger shapes (slower, more precise)")
     ap.add_argument("--readiness", action="store_true", help="fast numerics + memory check only")
     ap.add_argument("--matrix", default="bf16", help="comma-separated matrix data paths to check: bf16 (always), "
-                    "fp8, bf8, mxfp8, mxfp4, int8, fp64, sparse24")
+                    "fp8, bf8, mxfp8, mxfp4, int8, fp64, sparse24, fp32")
     ap.add_argument("--json", action="store_true")
     args = ap.parse_args(argv)
     matrix = tuple(m for m in args.matrix.split(",") if m)
